@@ -1,7 +1,13 @@
 """Benchmark: aggregate agent-steps/s of the device-resident greedy rollout (BASELINE.json config 3).
 
     python bench.py [--gpus N --steps K --warmup W]      (N > 1: starts the N ranks itself)
+    python bench.py --full [...]                         (the headline plus every other leg, below)
+    python bench.py --dump-outputs DIR [...]             (the last timed step's outputs as DIR/*.npy)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one rank per GPU)
+
+A plain run does what the headline needs and nothing else: set up, one dry run of the launches,
+the warmup, the K timed steps, the result line (ms_per_step = the timed window / K).  --full adds
+the other legs and the host-core baseline to the same line.
 
 Without a launcher, --gpus N > 1 makes this process start N child processes with
 torch.distributed.run's environment (launch_ranks; the parent touches no GPU); under a launcher,
@@ -15,6 +21,10 @@ policy+transition for every env; every step writes rewards [B,8] f32 and dones [
 nothing on the data path (no RCCL); a gloo group only aligns the timing window and takes the max.
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+  roofline     -- algorithmic bytes of the step kernel / its mean duration (HIP events on the
+                  launch stream), against the 8 TB/s HBM peak; `traffic` from the committed
+                  rocprofv3 PMC summary (profiles/) when present.
+and, with --full (each leg takes runs of its own; null without it),
   alt_launch_mode -- the same workload as a hipGraph of one-step launches (state through HBM)
   desync_episodes -- the headline launches after desynchronising the episodes (every step some
                   envs of each wave end and reset), with its kernel time relative to the headline
@@ -25,11 +35,16 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                   (wh_mlp_forward over all agent rows, then wh_vector_step), with the MLP kernel's
                   MFMA roofline (dense bf16 peak); policy_path_f32 the same with the exact-f32
                   network (f32 MFMA peak)
-  roofline     -- algorithmic bytes of the step kernel / its mean duration (HIP events on the
-                  launch stream), against the 8 TB/s HBM peak; `traffic` from the committed
-                  rocprofv3 PMC summary (profiles/) when present.
+  config_legs  -- BASELINE configs 2 and 4 through the headline's measurement.
   cpu_baseline -- the numpy restatement of warehouse.core.Warehouse.step() (oracle/core.py), one
                   env per process, step-only timing, on a bounded sample, rank 0 only.
+The legs that take --steps (alt_launch_mode, desync_episodes, config_legs) time at most --leg-steps
+of them, so a --full run stays bounded whatever --steps is.
+
+--dump-outputs DIR: after the timed steps, what a caller of the timed path holds after its last
+step -- that step's rewards [B,NA] and dones [B] and the env state behind them
+(BatchedWarehouse.to_canonical) -- one float32 DIR/<name>.npy each (dump_outputs).  The inputs are
+the same in every run with the same arguments (fixed seed, philox draws keyed by env id).
 """
 from __future__ import annotations
 
@@ -381,6 +396,11 @@ def window_setup_steps(T, K, pre):
     return (T - (K // 2) % T - pre) % T
 
 
+# Steps of the untimed dry run before a timed window (measure): the default --steps, so every window
+# up to that is rehearsed whole; a longer one does not pay its own length again before it starts.
+DRY_RUN_STEPS = 2000
+
+
 def launch_plan(K, chunk):
     """Steps per fused launch covering K steps."""
     plan = [chunk] * (K // chunk)
@@ -393,8 +413,10 @@ def measure(env, mode, policy, K, W, chunk, dev, world, dist, position=True):
     """Time K steps of `mode` (the contract's window).  The kernel time comes from HIP events recorded
     on the launch stream INSIDE that window around exactly the timed launches, so the roofline
     describes the launches that were timed.  Before the warmup, one untimed dry run of the same
-    launches, events and synchronisation warms the host path (it is part of the setup steps).
-    Returns a dict."""
+    launches (the first DRY_RUN_STEPS steps' worth of them), events and synchronisation warms the
+    host path (it is part of the setup steps).
+    Returns a dict; its `last_rewards` [B,NA] and `last_dones` [B] are the last timed step's outputs
+    (views of the buffers the timed launches wrote)."""
     import torch
 
     B, NA = env.B, env.agent_slots
@@ -422,8 +444,10 @@ def measure(env, mode, policy, K, W, chunk, dev, world, dist, position=True):
         torch.cuda.synchronize(dev)
         tail = env.rollout_launcher(1, policy, 0.0, rewards=rew1, dones=dn1)
         launches = [graph.replay] * (K // G) + [tail] * (K % G)
+        sizes = [G] * (K // G) + [1] * (K % G)
         plan = [1] * K
         dn = None
+        last = (rew1[0], dn1[0])
     else:
         plan = launch_plan(K, chunk)
         if whole:
@@ -437,18 +461,26 @@ def measure(env, mode, policy, K, W, chunk, dev, world, dist, position=True):
             o = off if whole else 0
             launches.append(env.rollout_launcher(c, policy, 0.0, rewards=rew[o:o + c], dones=dn[o:o + c]))
             off += c
+        sizes = plan
+        e = (K if whole else plan[-1]) - 1       # where the last launch wrote its last step
+        last = (rew[e], dn[e])
+    # the dry run: the leading launches, up to DRY_RUN_STEPS steps of them (the whole window for
+    # every K up to that; a longer window's host path is warm after them)
+    ndry = 1
+    while ndry < len(sizes) and sum(sizes[:ndry + 1]) <= DRY_RUN_STEPS:
+        ndry += 1
     # (events attached to the dispatch itself, wh_launch_run_timed, measured 7 us MORE window time per
     # launch than these two marker records: tools/launch_cost.py)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 
-    def run():
+    def run(n=None):
         ev0.record(stream)
-        for launch in launches:
+        for launch in launches[:n]:
             launch()
         ev1.record(stream)
 
-    timed_window(run, lambda: torch.cuda.synchronize(dev), world, dist)     # dry run (setup)
-    pre += K
+    timed_window(lambda: run(ndry), lambda: torch.cuda.synchronize(dev), world, dist)     # dry run (setup)
+    pre += sum(sizes[:ndry])
     setup = window_setup_steps(T, K, pre + W) if position else 0
     if setup:
         env.rollout(setup, policy, 0.0)           # position the window (untimed, no outputs)
@@ -469,7 +501,42 @@ def measure(env, mode, policy, K, W, chunk, dev, world, dist, position=True):
                 steps_per_launch=plan[0], bytes_per_launch=bytes_total / kernels,
                 achieved_gbs=bytes_total / (span_ms * 1e-3) / 1e9, bytes_per_env_step=bytes_total / (B * K),
                 host_fixed_us=(elapsed * 1e3 - span_ms) * 1e3, setup_steps=pre + setup,
-                window_t=[start, (start + K) % T], dones_in_window=dones)
+                window_t=[start, (start + K) % T], dones_in_window=dones,
+                last_rewards=last[0], last_dones=last[1])
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_sample(num_envs, bytes_per_env, budget):
+    """The envs whose outputs --dump-outputs writes: all of them (None) when bytes_per_env of each fit
+    the budget, else a fixed sample (numpy default_rng(0), sorted ids) that does."""
+    import numpy as np
+
+    if num_envs * bytes_per_env <= budget:
+        return None
+    return np.sort(np.random.default_rng(0).choice(num_envs, budget // bytes_per_env, replace=False))
+
+
+def dump_outputs(path, env, m, rank=0):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step of measure()
+    (dict m) -- that step's rewards [B,NA] and dones [B], and the state the launches left in env
+    (to_canonical: pos, agent_target, pickup_target, pickup_timer, t, n, fresh, episode) -- as float32
+    path/<name>.npy (<name>.rank<r>.npy for rank r > 0; every value is a small integer or a reward,
+    exact in float32).  More than DUMP_BUDGET_BYTES in all: the envs of dump_sample(), their ids in
+    env_index.npy (float64).  Call it before anything else steps env."""
+    import numpy as np
+
+    arrays = {"rewards": m["last_rewards"], "dones": m["last_dones"]}
+    arrays.update({f"state_{k}": v for k, v in env.to_canonical().items()})
+    arrays = {k: v.cpu().numpy().astype(np.float32) for k, v in arrays.items()}
+    pick = dump_sample(env.B, sum(a[0].size for a in arrays.values()) * 4 + 8, DUMP_BUDGET_BYTES)
+    if pick is not None:
+        arrays = {k: a[pick] for k, a in arrays.items()}
+        arrays["env_index"] = pick.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + (f".rank{rank}" if rank else "") + ".npy"), a)
 
 
 def measure_sampler(env, K, W, dev, world, dist):
@@ -934,6 +1001,16 @@ def main():
                     help="fused: --chunk steps per launch, state in registers (headline); "
                          "graph: hipGraph of one-step launches, state round-trips HBM every step")
     ap.add_argument("--chunk", type=int, default=200)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's rewards and dones and the env "
+                         "state behind them as DIR/<name>.npy (float32; at most 64 MB: a fixed sample of the "
+                         "envs beyond that)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every other leg (the other launch mode, desynchronised episodes, the "
+                         "sampler / vector / policy routes, configs C2 and C4) and the host-core baseline; "
+                         "without it the --no-* switches below have nothing to skip")
+    ap.add_argument("--leg-steps", type=int, default=2000,
+                    help="--full: the legs that take --steps time at most this many")
     ap.add_argument("--no-alt", action="store_true", help="skip the other launch mode")
     ap.add_argument("--no-sampler", action="store_true", help="skip the sampler-path (obs) measurement")
     ap.add_argument("--no-desync", action="store_true", help="skip the desynchronised-episodes measurement")
@@ -953,6 +1030,9 @@ def main():
                     help="self-test of the multi-rank plumbing without a GPU: no kernel runs, the window "
                          "times a host-side sleep; the line is marked as such")
     args = ap.parse_args()
+    if not args.full:   # a plain run: the headline alone
+        args.no_alt = args.no_sampler = args.no_desync = args.no_policy = args.no_configs = True
+        args.no_cpu_baseline = True
 
     # N ranks without a launcher: start them from here, before anything touches a GPU
     if check_world(args.gpus) == "launch":
@@ -987,13 +1067,19 @@ def main():
 
     m = measure(env, args.mode, args.policy, K, W, args.chunk, dev, world, dist)
     value = aggregate_rate(world, B, NA, K, m["elapsed"])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, m, rank)
+
+    # ---- everything below: --full only
+    Kl = min(K, args.leg_steps)
+    W = min(W, args.leg_steps)        # the legs' warmup likewise (the line reports args.warmup)
     alt = None
     if not args.no_alt:
         other = "graph" if args.mode == "fused" else "fused"
         env.reset()
-        m2 = measure(env, other, args.policy, K, W, args.chunk, dev, world, dist)
-        alt = {"mode": other, "value": aggregate_rate(world, B, NA, K, m2["elapsed"]),
-               "ms_per_step": m2["elapsed"] * 1e3 / K, "kernel_ms": m2["kernel_ms"],
+        m2 = measure(env, other, args.policy, Kl, W, args.chunk, dev, world, dist)
+        alt = {"mode": other, "value": aggregate_rate(world, B, NA, Kl, m2["elapsed"]), "steps": Kl,
+               "ms_per_step": m2["elapsed"] * 1e3 / Kl, "kernel_ms": m2["kernel_ms"],
                "steps_per_launch": m2["steps_per_launch"], "bytes_per_launch": m2["bytes_per_launch"],
                "roofline_frac": m2["achieved_gbs"] / HBM_PEAK_GBS, "host_fixed_us": m2["host_fixed_us"],
                "traffic": load_traffic(f"{args.variant}_n{NA}_{other}_k{m2['steps_per_launch']}")}
@@ -1011,13 +1097,13 @@ def main():
         # three windows in a row (the episodes stay desynchronised), the median by kernel time: one
         # 20-step window on a box whose clock is settling read anywhere from 1.07x to 1.48x of the
         # synchronised launch with identical code (profiles/r04_desync20_ab.txt)
-        runs = [measure(env, "fused", args.policy, K, W, args.chunk, dev, world, dist, position=False) for _ in range(3)]
+        runs = [measure(env, "fused", args.policy, Kl, W, args.chunk, dev, world, dist, position=False) for _ in range(3)]
         md = sorted(runs, key=lambda r: r["kernel_ms"])[1]
-        vd = aggregate_rate(world, B, NA, K, md["elapsed"])
+        vd = aggregate_rate(world, B, NA, Kl, md["elapsed"])
         desync = {"workload": "same launches after BatchedWarehouse.stagger: env e is 37e mod T steps ahead, so "
                               "the lanes of every wave are spread over the episode and about B/T envs end "
                               "their episode on every step",
-                  "value": vd, "ms_per_step": md["elapsed"] * 1e3 / K, "kernel_ms": md["kernel_ms"],
+                  "value": vd, "steps": Kl, "ms_per_step": md["elapsed"] * 1e3 / Kl, "kernel_ms": md["kernel_ms"],
                   "dones_in_window": md["dones_in_window"], "host_fixed_us": md["host_fixed_us"],
                   "kernel_time_vs_synchronised": md["kernel_ms"] / m["kernel_ms"],
                   "kernel_ms_windows": [r["kernel_ms"] for r in runs]}
@@ -1087,8 +1173,8 @@ def main():
     # BASELINE configs 2 and 4 through the headline's measurement, in the same run (C3 is the headline)
     legs = {}
     if not args.no_configs and (args.variant, NA, B, args.policy) == ("medium", 8, 65536, "greedy"):
-        legs["C2"] = config_leg("C2", "small", 4, 4096, "random", K, W, args.chunk, dev, world, dist, rank)
-        legs["C4"] = config_leg("C4", "large", 16, 65536, "greedy", K, W, args.chunk, dev, world, dist, rank)
+        legs["C2"] = config_leg("C2", "small", 4, 4096, "random", Kl, W, args.chunk, dev, world, dist, rank)
+        legs["C4"] = config_leg("C4", "large", 16, 65536, "greedy", Kl, W, args.chunk, dev, world, dist, rank)
 
     # the RLlib route of scripts/train.py's actual env (all three registered names build
     # WarehouseLargeTrain, scripts/train.py:34-35): external actions, n redrawn at every auto-reset
@@ -1149,8 +1235,9 @@ def main():
             "unit": "agent-steps/s",
             "n_gpus": world,
             "steps": K,
-            "warmup": W,
+            "warmup": args.warmup,
             "ms_per_step": m["elapsed"] * 1e3 / K,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -35,6 +35,65 @@ def test_profiles_are_pinned_to_the_kernel_sources(tmp_path, monkeypatch):
     assert bench.load_profile("no_such_tag") is None
 
 
+def test_plain_run_skips_what_full_adds(monkeypatch, capsys):
+    """Without --full the line carries no host-core baseline (nor any other leg: tests/test_gpu_bench.py);
+    with it, the baseline is back.  --plumbing-only: the same report path with no kernel."""
+    import json
+    import sys
+
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    calls = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a: calls.append(a) or {"value": 2.0})
+    for extra in ([], ["--full"], ["--full", "--no-cpu-baseline"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--plumbing-only", "--steps", "4", "--warmup", "1"] + extra)
+        bench.main()
+        line = json.loads(capsys.readouterr().out.splitlines()[-1])
+        assert line["steps"] == 4 and line["ms_per_step"] * 4 >= 50.0
+        assert ("cpu_baseline" in line) == (extra == ["--full"])
+    assert len(calls) == 1
+
+
+def test_dump_outputs_writes_float32_arrays_within_the_budget(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+
+    B, NA, P = 50, 3, 4
+
+    class Env:
+        def to_canonical(self):
+            return {"pos": torch.arange(B * NA * 2, dtype=torch.int32).view(B, NA, 2),
+                    "pickup_target": torch.arange(B * P, dtype=torch.int32).view(B, P) - 1,
+                    "t": torch.arange(B, dtype=torch.int32)}
+
+    env = Env()
+    env.B = B
+    m = {"last_rewards": torch.arange(B * NA, dtype=torch.float32).view(B, NA) / 4,
+         "last_dones": (torch.arange(B) % 3 == 0).to(torch.uint8)}
+    bench.dump_outputs(str(tmp_path / "all"), env, m)
+    got = {f: np.load(tmp_path / "all" / f) for f in ("rewards.npy", "dones.npy", "state_pos.npy",
+                                                       "state_pickup_target.npy", "state_t.npy")}
+    assert sorted(got) == sorted(p.name for p in (tmp_path / "all").iterdir())
+    assert all(a.dtype == np.float32 for a in got.values())
+    np.testing.assert_array_equal(got["rewards.npy"], m["last_rewards"].numpy())
+    np.testing.assert_array_equal(got["dones.npy"], m["last_dones"].numpy())
+    np.testing.assert_array_equal(got["state_pos.npy"], env.to_canonical()["pos"].numpy())
+    # over the budget: the same fixed sample of envs in every array, its ids alongside
+    per_env = (NA + 1 + NA * 2 + P + 1) * 4 + 8
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 20 * per_env + 5)
+    bench.dump_outputs(str(tmp_path / "s1"), env, m)
+    bench.dump_outputs(str(tmp_path / "s2"), env, m, rank=1)
+    ids = np.load(tmp_path / "s1" / "env_index.npy")
+    assert ids.dtype == np.float64 and len(ids) == 20 and np.all(np.diff(ids) > 0) and ids[-1] < B
+    np.testing.assert_array_equal(ids, np.load(tmp_path / "s2" / "env_index.rank1.npy"))
+    pick = ids.astype(int)
+    np.testing.assert_array_equal(np.load(tmp_path / "s1" / "rewards.npy"), m["last_rewards"].numpy()[pick])
+    np.testing.assert_array_equal(np.load(tmp_path / "s2" / "state_t.rank1.npy"), pick)
+    total = sum(p.stat().st_size for p in (tmp_path / "s1").iterdir())
+    assert total <= bench.DUMP_BUDGET_BYTES + 128 * 6          # + one .npy header per file
+    assert bench.dump_sample(B, per_env, B * per_env) is None
+
+
 def test_step_roofline_names_the_binding_resource(monkeypatch):
     """roofline.valu = SQ_INSTS_VALU per launch / kernel time against 1,024 SIMDs x 1.2 G wave64-VALU/s;
     `bound` is the larger of the VALU and HBM fractions, both reported."""

@@ -173,13 +173,14 @@ def bench_overrides():
 def test_bench_self_launches_n_ranks_without_a_launcher():
     """`python bench.py --gpus 2` with no torch.distributed.run around it starts both ranks itself (from
     a parent that never touches a GPU), and rank 0 prints ONE line with n_gpus 2, the max-over-ranks
-    window and the host-core baseline.  --plumbing-only runs that path with no kernel (CPU here)."""
+    window and, with --full, the host-core baseline.  --plumbing-only runs that path with no kernel
+    (CPU here)."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--plumbing-only",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--plumbing-only", "--full",
                         "--steps", "20", "--warmup", "5", "--cpu-procs", "1", "--cpu-seconds", "0.3"],
                        cwd=root, env=_bench_env(), capture_output=True, text=True, timeout=500)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,6 +7,6 @@ OUT=gpurun_out/configs.jsonl
 : > $OUT
 run() { timeout -k 10 600 "$@" 2>/dev/null | tail -1 >> $OUT; }
 run python tools/dropin_c1.py && \
-run python bench.py --variant small --agents 4 --envs 4096 --policy random --no-alt --no-sampler --no-policy --no-cpu-baseline && \
-run python bench.py --no-alt --no-sampler --no-policy --no-cpu-baseline && \
-run python bench.py --variant large --agents 16 --no-alt --no-sampler --no-policy --no-cpu-baseline
+run python bench.py --variant small --agents 4 --envs 4096 --policy random --full --no-alt --no-sampler --no-policy --no-cpu-baseline && \
+run python bench.py --full --no-alt --no-sampler --no-policy --no-cpu-baseline && \
+run python bench.py --variant large --agents 16 --full --no-alt --no-sampler --no-policy --no-cpu-baseline

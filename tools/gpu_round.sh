@@ -19,7 +19,7 @@ for s in "$@"; do
   case "$s" in
     smoke)  step smoke 420 python -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) step pytest 1100 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --timeout 300 --timeout-method thread ;;
-    bench)  step bench 600 python bench.py ;;
+    bench)  step bench 600 python bench.py --full ;;
     *)      step custom$i 900 bash -c "$s" ;;
   esac
 done

@@ -15,7 +15,7 @@ run() { local name=$1 limit=$2; shift 2
   timeout -k 10 $limit "$@" > $OUT/$name.log 2>&1; local rc=$?
   echo "$name rc=$rc" | tee -a $OUT/status.txt
   [ $rc -eq 0 ] || exit $rc; }
-run driver 500 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/driver -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5
+run driver 500 rocprofv3 --kernel-trace --stats -T --output-format csv -d $OUT/driver -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5
 SQ="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_VALU"
 SQ2="SQ_WAVES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES"
 for shape in ${2:-medium:8:20 medium:8:200 large:16:20}; do

@@ -11,6 +11,6 @@ P3="SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_SALU
 i=0
 for P in "$P1" "$P2" "$P3"; do
   i=$((i+1))
-  timeout -k 10 600 rocprofv3 --pmc $P -T --output-format csv -d $OUT/p$i -o run -- python3 bench.py --no-cpu-baseline --steps 400 --warmup 20 "$@" > $OUT/p$i.log 2>&1
+  timeout -k 10 600 rocprofv3 --pmc $P -T --output-format csv -d $OUT/p$i -o run -- python3 bench.py --full --no-cpu-baseline --steps 400 --warmup 20 "$@" > $OUT/p$i.log 2>&1
   rc=$?; echo "pass $i rc=$rc" | tee -a $OUT/status.txt; [ $rc -eq 0 ] || exit $rc
 done
