@@ -8,7 +8,8 @@
  * (NULL = the default stream).  The host engine (libwarehouse_host.so, csrc/host_engine.cpp: the
  * same entry points on host cores, for hosts without a GPU) takes host memory for every "device"
  * pointer, ignores `stream`, runs synchronously, and returns WH_ENOTSUP for the device-only entry
- * points (policy network, fragment operand, two-stream and prepared launches, assert mode).
+ * points (policy network, fragment operand, two-stream and prepared launches, assert mode, the
+ * 16-lanes-per-env execution form wh_*_wide).
  * All calls are asynchronous on `stream` except where noted, return
  * WH_OK (0) or a WH_E* code, and never throw.  The reference is Python, so the binding a maintainer
  * adds on the reference side is ctypes; `warehouse/_native.py` is that binding.
@@ -228,6 +229,30 @@ int wh_sampler_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t
 int wh_sampler_step_to(const wh_config* cfg, int64_t B, const uint32_t* state_in, uint32_t* state_out,
                        int32_t policy, float p, float* rewards, uint8_t* dones, const wh_episode_stats* stats,
                        int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream);
+
+/* A second execution form of the step for small batches: one env spread over WH_WIDE_LANES lanes (4 envs
+ * per wave, 16 per workgroup; csrc/step_wide.h) instead of one env per lane, so the per-agent and
+ * per-pickup phases of a step take O(1) lane steps.  Same packed state, philox contract, outputs and
+ * transitions, bit for bit: a wide launch and a lane-per-env launch may alternate on one state buffer.
+ * Each entry mirrors the one it is named after (ascending agent order, the whole step: no `order`, no
+ * split phases, no state_out, no fused observation rows) with a trailing `lanes`:
+ *   lanes == WH_WIDE_LANES  the wide kernel;
+ *   lanes == 1              the lane-per-env entry point itself (order = NULL, WH_PHASE_ALL);
+ *   anything else           WH_EINVAL.
+ * wh_step_wide writes n_inactive (when not NULL) although it runs the whole step.  wh_vector_step_wide
+ * is the wide step launch followed by wh_observe (obs may be NULL).  Device only. */
+#define WH_WIDE_LANES 16
+int wh_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, float* rewards,
+                 uint8_t* dones, const int32_t* regen, int32_t* n_inactive, uint64_t seed, int64_t env_offset,
+                 int32_t lanes, void* stream);
+int wh_rollout_wide(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
+                    float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
+                    int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes,
+                    void* stream);
+int wh_vector_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
+                        const uint8_t* mask, float* rewards, uint8_t* dones, float* obs,
+                        const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
+                        int64_t env_offset, int32_t lanes, void* stream);
 
 /* A prepared wh_rollout: the same arguments resolved once (config validated, kernel and tables
  * chosen) into an opaque handle, so a loop that launches the same rollout repeatedly pays one

@@ -8,7 +8,8 @@
 // (packed state layout, injected draws, the philox draw contract of the device kernels) -- not a
 // translation of the test oracle, which it never calls.  Every pointer is host memory and `stream`
 // is ignored.  Entry points the CPU has no use for (the policy network, the fragment operand, the
-// two-stream sampler step wh_sampler_step_to, prepared launches, assert mode) return WH_ENOTSUP;
+// two-stream sampler step wh_sampler_step_to, prepared launches, assert mode, the 16-lanes-per-env
+// entries wh_*_wide) return WH_ENOTSUP;
 // wh_sampler_step / wh_sampler_rollout run as policy + vector step per env.
 //
 // The state is the device's packed word planes (state[w * B + e]), so a state can move between the
@@ -890,6 +891,31 @@ int wh_mlp_forward_x(const wh_mlp_desc* d, const void* packed, int64_t rows, con
 }
 int wh_check_read(uint64_t* out, int32_t clear) {
   (void)out, (void)clear;
+  return WH_ENOTSUP;
+}
+
+// The 16-lanes-per-env form is a device execution form (csrc/step_wide.h): the host engine has no lanes.
+int wh_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, float* rewards,
+                 uint8_t* dones, const int32_t* regen, int32_t* n_inactive, uint64_t seed, int64_t env_offset,
+                 int32_t lanes, void* stream) {
+  (void)cfg, (void)B, (void)state, (void)actions, (void)rewards, (void)dones, (void)regen, (void)n_inactive,
+      (void)seed, (void)env_offset, (void)lanes, (void)stream;
+  return WH_ENOTSUP;
+}
+int wh_rollout_wide(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
+                    float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
+                    int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes,
+                    void* stream) {
+  (void)cfg, (void)B, (void)state, (void)steps, (void)policy, (void)p, (void)rewards, (void)dones, (void)returns,
+      (void)stats, (void)autoreset, (void)variable_n, (void)seed, (void)env_offset, (void)lanes, (void)stream;
+  return WH_ENOTSUP;
+}
+int wh_vector_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
+                        const uint8_t* mask, float* rewards, uint8_t* dones, float* obs,
+                        const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
+                        int64_t env_offset, int32_t lanes, void* stream) {
+  (void)cfg, (void)B, (void)state, (void)actions, (void)mask, (void)rewards, (void)dones, (void)obs, (void)stats,
+      (void)autoreset, (void)variable_n, (void)seed, (void)env_offset, (void)lanes, (void)stream;
   return WH_ENOTSUP;
 }
 

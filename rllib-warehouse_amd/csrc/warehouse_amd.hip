@@ -1675,6 +1675,9 @@ __device__ __forceinline__ void flush_episodes(bool fin, uint32_t n, uint32_t re
   }
 }
 
+// The 16-lanes-per-env form of the step (k_step_wide): wh_step_wide / wh_rollout_wide / wh_vector_step_wide.
+#include "step_wide.h"
+
 // The step loop of k_step.  PHASE >= 0 fixes the phase at compile time (the fused rollout and the
 // sampler path run PH_ALL), so the phase tests fold away and each step is a few large basic blocks
 // the scheduler can interleave; -1 reads it from the launch (the drop-in's split step).  Phase
@@ -2782,6 +2785,7 @@ struct Kernels {
   void (*step[3])(StepParams);
   void (*step_fast[3])(StepParams);   // [policy]: greedy / random fused rollouts (NAM even), else null
   void (*step_ordered)(StepParams);
+  void (*step_wide[3])(StepParams);   // [policy]: 16 lanes per env (k_step_wide)
   void (*sampler[3])(StepParams, float*);   // [policy]: fused step + rows (k_sampler), NAM even, else null
   void (*sampler_multi[3])(StepParams, float*);   // [policy]: the same, K steps per launch (greedy / random)
   void (*vsampler[2])(StepParams, float*);  // [ordered]: wh_vector_step's step + rows (external actions)
@@ -2828,6 +2832,9 @@ Kernels make_kernels() {
     k.step_fast[1] = k.step_fast[2] = nullptr;
   }
   k.step_ordered = k_step<C, POL_EXTERNAL, true, false>;
+  k.step_wide[0] = k_step_wide<C, POL_EXTERNAL>;
+  k.step_wide[1] = k_step_wide<C, POL_GREEDY>;
+  k.step_wide[2] = k_step_wide<C, POL_RANDOM>;
   k.vsampler[0] = k.vsampler[1] = nullptr;
   if constexpr (kSamplerBuilt<C>) {
     k.vsampler[0] = k_sampler<C, POL_EXTERNAL, false, false>;
@@ -2912,6 +2919,7 @@ int prepare(const wh_config* cfg, int64_t B, void* stream, Geometry* g, const Ke
 }
 
 inline dim3 grid_for(int64_t B) { return dim3((unsigned)((B + BT - 1) / BT)); }
+inline dim3 grid_wide(int64_t B) { return dim3((unsigned)((B + WIDE_ENVS - 1) / WIDE_ENVS)); }   // k_step_wide: 16 envs per workgroup
 
 }  // namespace
 
@@ -3055,7 +3063,7 @@ static bool launch_live(const wh_launch* l) {
 }
 
 static int resolve_step(const wh_config* cfg, int64_t B, uint32_t* state, int policy, StepParams a,
-                        void* stream, wh_launch* out) {
+                        void* stream, wh_launch* out, int lanes = 1) {
   Geometry g;
   const Kernels* k;
   const uint32_t* tab;
@@ -3086,8 +3094,8 @@ static int resolve_step(const wh_config* cfg, int64_t B, uint32_t* state, int po
       !a.stats.episode_return && !a.mask && !a.order && !a.regen && !a.n_inactive && a.autoreset &&
       g.NA == k->NAM && ((uintptr_t)a.rewards & ralign) == 0)
     kern = k->step_fast[policy];
-  out->kern = kern;
-  out->grid = grid_for(B);
+  out->kern = lanes == WH_WIDE_LANES ? k->step_wide[policy] : kern;
+  out->grid = lanes == WH_WIDE_LANES ? grid_wide(B) : grid_for(B);
   out->stream = (hipStream_t)stream;
   out->a = a;
   return WH_OK;
@@ -3100,9 +3108,9 @@ static int enqueue(const wh_launch& l) {
 }
 
 static int launch_step(const wh_config* cfg, int64_t B, uint32_t* state, int policy,
-                       StepParams a, void* stream) {
+                       StepParams a, void* stream, int lanes = 1) {
   wh_launch l;
-  const int rc = resolve_step(cfg, B, state, policy, a, stream, &l);
+  const int rc = resolve_step(cfg, B, state, policy, a, stream, &l, lanes);
   return rc ? rc : enqueue(l);
 }
 
@@ -3445,6 +3453,86 @@ int wh_sampler_step_to(const wh_config* cfg, int64_t B, const uint32_t* state_in
   a.variable_n = variable_n ? 1 : 0;
   a.state_out = state_out;   // every env is live (no mask): each lane stores its whole state
   return launch_step(cfg, B, const_cast<uint32_t*>(state_in), policy, a, stream);
+}
+
+
+// ---- the 16-lanes-per-env execution form (csrc/step_wide.h).  lanes == WH_WIDE_LANES runs
+// k_step_wide; lanes == 1 is the lane-per-env entry point itself (ascending order, whole step).
+int wh_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, float* rewards,
+                 uint8_t* dones, const int32_t* regen, int32_t* n_inactive, uint64_t seed, int64_t env_offset,
+                 int32_t lanes, void* stream) {
+  if (lanes == 1)
+    return wh_step(cfg, B, state, actions, nullptr, 0, rewards, dones, regen, n_inactive, WH_PHASE_ALL, seed,
+                   env_offset, stream);
+  if (lanes != WH_WIDE_LANES) return WH_EINVAL;
+  if (B > 0 && !actions) return WH_EINVAL;
+  StepParams a{};
+  a.actions = actions;
+  a.rewards = rewards;
+  a.dones = dones;
+  a.regen = regen;
+  a.n_inactive = n_inactive;
+  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
+  a.k1 = (uint32_t)(seed >> 32);
+  a.env_offset = env_offset;
+  a.steps = 1;
+  a.phase = PH_ALL;
+  return launch_step(cfg, B, state, POL_EXTERNAL, a, stream, lanes);
+}
+
+int wh_rollout_wide(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
+                    float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
+                    int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes,
+                    void* stream) {
+  if (lanes == 1)
+    return wh_rollout(cfg, B, state, steps, policy, p, rewards, dones, returns, stats, autoreset, variable_n, seed,
+                      env_offset, stream);
+  if (lanes != WH_WIDE_LANES) return WH_EINVAL;
+  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || steps < 0) return WH_EINVAL;
+  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
+  StepParams a{};
+  if (stats) a.stats = *stats;
+  a.rewards = rewards;
+  a.dones = dones;
+  a.returns = returns;
+  a.p = p;
+  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
+  a.k1 = (uint32_t)(seed >> 32);
+  a.env_offset = env_offset;
+  a.steps = steps;
+  a.phase = PH_ALL;
+  a.autoreset = autoreset ? 1 : 0;
+  a.variable_n = variable_n ? 1 : 0;
+  return launch_step(cfg, B, state, policy, a, stream, lanes);
+}
+
+// the wide step launch, then k_observe (wh_observe): two launches
+int wh_vector_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
+                        const uint8_t* mask, float* rewards, uint8_t* dones, float* obs,
+                        const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
+                        int64_t env_offset, int32_t lanes, void* stream) {
+  if (lanes == 1)
+    return wh_vector_step(cfg, B, state, actions, nullptr, 0, mask, rewards, dones, obs, stats, autoreset,
+                          variable_n, seed, env_offset, stream);
+  if (lanes != WH_WIDE_LANES) return WH_EINVAL;
+  if (B > 0 && !actions) return WH_EINVAL;
+  if (!stats_ok(stats)) return WH_EINVAL;
+  StepParams a{};
+  a.actions = actions;
+  a.mask = mask;
+  a.rewards = rewards;
+  a.dones = dones;
+  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
+  a.k1 = (uint32_t)(seed >> 32);
+  a.env_offset = env_offset;
+  a.steps = 1;
+  a.phase = PH_ALL;
+  a.autoreset = autoreset ? 1 : 0;
+  a.variable_n = variable_n ? 1 : 0;
+  if (stats) a.stats = *stats;
+  const int rc = launch_step(cfg, B, state, POL_EXTERNAL, a, stream, lanes);
+  if (rc || !obs) return rc;
+  return wh_observe(cfg, B, state, obs, stream);
 }
 
 }  // extern "C"

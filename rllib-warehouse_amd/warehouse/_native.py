@@ -36,12 +36,15 @@ WH_PHASE_REGEN = 2
 WH_POLICY_GREEDY = 1
 WH_POLICY_RANDOM = 2
 
+WH_WIDE_LANES = 16   # lanes per env of the wide step form (wh_*_wide); 1 = the lane-per-env kernels
+
 # every symbol include/warehouse_amd.h declares
 SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observe", "wh_policy",
            "wh_rollout", "wh_vector_step", "wh_mlp_query", "wh_mlp_pack", "wh_mlp_forward", "wh_version",
            "wh_observe_x", "wh_mlp_forward_x",
            "wh_check_read", "wh_rollout_prepare", "wh_launch_run", "wh_launch_run_timed", "wh_launch_free",
-           "wh_sampler_step", "wh_sampler_step_to", "wh_sampler_rollout", "wh_vector_step_x")
+           "wh_sampler_step", "wh_sampler_step_to", "wh_sampler_rollout", "wh_vector_step_x",
+           "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide")
 
 
 class WhConfig(ctypes.Structure):
@@ -164,6 +167,10 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_sampler_step.argtypes = [_CFG, _I64, _P, _I32, _F32, _P, _P, _P, _ST, _I32, _U64, _I64, _P]
     S.wh_sampler_step_to.argtypes = [_CFG, _I64, _P, _P, _I32, _F32, _P, _P, _ST, _I32, _U64, _I64, _P]
     S.wh_sampler_rollout.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _U64, _I64, _P]
+    # the 16-lanes-per-env form: the entry it mirrors without order / phase, `lanes` before the stream
+    S.wh_step_wide.argtypes = [_CFG, _I64, _P, _P, _P, _P, _P, _P, _U64, _I64, _I32, _P]
+    S.wh_rollout_wide.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _I32, _P]
+    S.wh_vector_step_wide.argtypes = [_CFG, _I64, _P, _P, _P, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _I32, _P]
     _MD = ctypes.POINTER(WhMlpDesc)
     S.wh_mlp_query.argtypes = [_MD, ctypes.POINTER(ctypes.c_int64)]
     S.wh_mlp_pack.argtypes = [_MD] + [_P] * 7

@@ -12,6 +12,7 @@ device is visible (BASELINE config 1).  Same entry points, state layout and draw
     policy()   -> wh_policy   greedy / random actions        baseline/solvers.py:27-58
     rollout()  -> wh_rollout  device-resident rollout loop   baseline/run.py:42-62
     vector_step() -> wh_vector_step  sampler step: step + auto-reset + observation rows
+    lanes_per_env=16 -> wh_step_wide / wh_rollout_wide / wh_vector_step_wide: the same step, 16 lanes per env
     EpisodeStats     on_episode_end metrics kept on the device  scripts/train.py:18-23
 
 Global env ids are `env_offset + e`; with philox draws a shard of env ids reproduces exactly the
@@ -155,11 +156,24 @@ def custom_metrics_from_bins(return_sum, episodes, return_min, return_max) -> Di
 
 class BatchedWarehouse:
     """`num_envs` episodes of one variant.  `train=True` gives the Train variants' per-episode
-    agent count n ~ U{1..max_num_agents} (warehouse/variants.py:65-98) with max_num_agents slots."""
+    agent count n ~ U{1..max_num_agents} (warehouse/variants.py:65-98) with max_num_agents slots.
+
+    `lanes_per_env` picks the execution form of the step on a HIP device: 1 (default) the
+    lane-per-env kernels, 16 the wide kernel (csrc/step_wide.h: one env over 16 lanes, for small
+    batches below one wave per SIMD).  Same transitions, draws and state either way.  With 16,
+    step(), rollout() and vector_step() -- and so stagger(), which steps through vector_step() with a
+    mask -- call wh_step_wide / wh_rollout_wide / wh_vector_step_wide; the wide form runs the whole
+    step in ascending agent order only, so `order=` or `phase != WH_PHASE_ALL` raise ValueError
+    (no silent switch of kernels).  policy(), observe*(), reset(), vector_step_x(), sampler_*() and
+    rollout_launcher() keep the lane-per-env kernels.  The host engine has no lanes: 16 with
+    device="cpu" raises."""
 
     def __init__(self, variant: str = "medium", num_envs: int = 1, num_agents: Optional[int] = None,
                  *, train: bool = False, seed: int = 0, env_offset: int = 0, device=None,
-                 geometry: Optional[dict] = None):
+                 geometry: Optional[dict] = None, lanes_per_env: int = 1):
+        if lanes_per_env not in (1, nat.WH_WIDE_LANES):
+            raise ValueError(f"lanes_per_env: 1 or {nat.WH_WIDE_LANES}, got {lanes_per_env!r}")
+        self.lanes_per_env = int(lanes_per_env)
         geo = dict(GEOMETRY[variant] if geometry is None else geometry)
         self.geometry = geo
         self.variant = variant if geometry is None else None
@@ -172,6 +186,8 @@ class BatchedWarehouse:
         self.cfg = nat.make_config(geo["D"], geo["R"], geo["racks"], slots, geo["T"], geo["W"])
         self.device = resolve_device(device)
         self.host = self.device.type == "cpu"          # the host engine (no HIP device)
+        if self.host and self.lanes_per_env != 1:
+            raise ValueError("lanes_per_env=16 is a device execution form: the host engine (device='cpu') has no lanes")
         self._lib = nat.host_lib() if self.host else nat.lib()
         self.layout = nat.query(self.cfg, self._lib)
         self.B = int(num_envs)
@@ -246,6 +262,17 @@ class BatchedWarehouse:
         """One transition for every env.  actions [B,NA] in 0..8; order [B,OL] (OL up to 4 NA, -1
         padded) is the action-dict iteration order; regen [B,2R] injects the regeneration draws.
         Returns the env-owned (rewards [B,NA] float32, dones [B] uint8) buffers, overwritten next call."""
+        if self.lanes_per_env != 1:
+            if order is not None:
+                raise ValueError("step: `order` is not supported with lanes_per_env=16 (ascending agent order only)")
+            if int(phase) != nat.WH_PHASE_ALL:
+                raise ValueError("step: `phase` other than WH_PHASE_ALL is not supported with lanes_per_env=16")
+            a = _dev_i32(actions, self.device, (self.B, self.agent_slots))
+            r = _dev_i32(regen, self.device, (self.B, 2 * self.R))
+            self._call("wh_step_wide", self.state.data_ptr(), self._ptr(a), self.rewards.data_ptr(),
+                       self.dones.data_ptr(), self._ptr(r), self.n_inactive.data_ptr(), self.seed, self.env_offset,
+                       self.lanes_per_env, self.stream)
+            return self.rewards, self.dones
         a = None if actions is None else _dev_i32(actions, self.device, (self.B, self.agent_slots))
         o, ol = self._order(order)
         r = _dev_i32(regen, self.device, (self.B, 2 * self.R))
@@ -291,6 +318,8 @@ class BatchedWarehouse:
         Returns env-owned (obs [B,NA,9R+1] or None, rewards [B,NA], dones [B]); with autoreset the
         obs rows of a done env already belong to its next episode.  Rewards/dones of envs outside
         `mask` are stale."""
+        if self.lanes_per_env != 1 and order is not None:
+            raise ValueError("vector_step: `order` is not supported with lanes_per_env=16 (ascending agent order only)")
         a = _dev_i32(actions, self.device, (self.B, self.agent_slots))
         o, ol = self._order(order)
         m = _dev_mask(mask, self.device, self.B)
@@ -298,6 +327,13 @@ class BatchedWarehouse:
             self._obs = torch.empty((self.B, self.agent_slots, self.obs_len), dtype=torch.float32,
                                     device=self.device)
         obs = self._obs if observe else None
+        if self.lanes_per_env != 1:
+            self._call("wh_vector_step_wide", self.state.data_ptr(), a.data_ptr(), self._ptr(m),
+                       self.rewards.data_ptr(), self.dones.data_ptr(), self._ptr(obs),
+                       None if self.stats is None else self.stats.ref,
+                       int(bool(autoreset)), int(self.train), self.seed, self.env_offset, self.lanes_per_env,
+                       self.stream)
+            return obs, self.rewards, self.dones
         self._call("wh_vector_step", self.state.data_ptr(), a.data_ptr(), self._ptr(o), ol, self._ptr(m),
                    self.rewards.data_ptr(), self.dones.data_ptr(), self._ptr(obs),
                    None if self.stats is None else self.stats.ref,
@@ -365,6 +401,12 @@ class BatchedWarehouse:
                             (dones, (steps, self.B), torch.uint8), (returns, (self.B,), torch.float32)):
             if t is not None:
                 _check_out(t, shape, d, self.device)
+        if self.lanes_per_env != 1:
+            self._call("wh_rollout_wide", self.state.data_ptr(), int(steps), POLICIES[policy], float(p),
+                       self._ptr(rewards), self._ptr(dones), self._ptr(returns),
+                       None if self.stats is None else self.stats.ref, int(bool(autoreset)),
+                       int(self.train), self.seed, self.env_offset, self.lanes_per_env, self.stream)
+            return
         self._call("wh_rollout", self.state.data_ptr(), int(steps), POLICIES[policy], float(p),
                    self._ptr(rewards), self._ptr(dones), self._ptr(returns),
                    None if self.stats is None else self.stats.ref, int(bool(autoreset)),

@@ -71,13 +71,14 @@ def unflatten_row(row: np.ndarray, R: int) -> Dict[str, np.ndarray]:
 class WarehouseVectorEnv:
     """`num_envs` episodes of one variant as a vectorised sampler env (tensor API).  Train
     variants (default, like scripts/train.py:11-15) draw each episode's agent count n on the
-    device; rows and rewards of slots >= n are zero and `agent_mask()` marks the live ones."""
+    device; rows and rewards of slots >= n are zero and `agent_mask()` marks the live ones.
+    `lanes_per_env` is BatchedWarehouse's (16: the wide step kernel, which takes no `order`)."""
 
     def __init__(self, variant: str = "medium", num_envs: int = 1024, num_agents: Optional[int] = None,
                  *, train: bool = True, seed: int = 0, env_offset: int = 0, device=None,
-                 autoreset: bool = True):
+                 autoreset: bool = True, lanes_per_env: int = 1):
         self.env = BatchedWarehouse(variant, num_envs, num_agents, train=train, seed=seed,
-                                    env_offset=env_offset, device=device)
+                                    env_offset=env_offset, device=device, lanes_per_env=lanes_per_env)
         geo = GEOMETRY[variant]
         self.variant = variant
         self.num_envs = self.env.B
