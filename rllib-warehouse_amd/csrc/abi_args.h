@@ -1,0 +1,216 @@
+// abi_args.h -- the argument rules of the C ABI (include/warehouse_amd.h), written once for the two
+// libraries behind it: the gfx950 library (warehouse_amd.hip) and the host engine (host_engine.cpp).
+// Plain C++17, no HIP.  What is here is a property of the ABI, not of a back end: which configs
+// are valid and the sizes that follow from one, which option values an entry point refuses, and a
+// step-family call checked and reduced to one struct (StepCall) that a back end then runs.  What a
+// back end cannot run -- no kernel instance for a geometry, racks that overlap, the host engine's
+// 64-point sets -- it refuses itself, after these checks.
+//
+// Order of the checks, hence the code returned when several things are wrong at once: `lanes`, the
+// entry point's own options and required pointers (WH_EINVAL), the config (WH_EINVAL, or
+// WH_ENOTSUP for racks on the border), the state pointer, the order-row width, B < 0 (WH_EINVAL);
+// then the back end's refusals.  Only the pointer checks depend on the batch: a bad option or config
+// is refused for an empty batch (B = 0 or steps = 0) like for a full one.
+#pragma once
+#include <stdint.h>
+
+#include "warehouse_amd.h"
+
+namespace wh_abi {
+
+// ----------------------------------------------------------------------------- config
+struct Shape {   // a valid wh_config and the sizes that follow from it
+  int D, R, NR, NA, T, W;
+  int P, DP;     // pickup points 4 NR^2 (core.py:171-175), delivery points 4 (D - 4) (core.py:178-188)
+  int L, words;  // floats per observation row 9 R + 1, packed state words per env
+  int racks[WH_MAX_RACKS];
+};
+
+inline int check_config(const wh_config* c, Shape* g) {
+  if (!c) return WH_EINVAL;
+  g->D = c->area_dimension;
+  g->R = c->num_requests;
+  g->NR = c->num_racks;
+  g->NA = c->agent_slots;
+  g->T = c->episode_duration;
+  g->W = c->pickup_wait_duration;
+  if (g->NR < 1 || g->NR > WH_MAX_RACKS || g->D < 5 || g->D > 32) return WH_EINVAL;
+  g->P = 4 * g->NR * g->NR;
+  g->DP = 4 * (g->D - 4);
+  if (g->NA < 1 || g->NA > g->R || g->R > g->P || g->R > g->DP) return WH_EINVAL;
+  if (g->W < 1 || g->W > 255 || g->T < 0) return WH_EINVAL;
+  for (int i = 0; i < g->NR; ++i) {
+    g->racks[i] = c->racks[i];
+    if (c->racks[i] < 2 || c->racks[i] > g->D - 2) return WH_ENOTSUP;   // pickups must be interior
+  }
+  g->L = 9 * g->R + 1;
+  g->words = 2 + g->NA + 2 * (g->P / 4);
+  return WH_OK;
+}
+
+// ----------------------------------------------------------------------------- option values
+inline bool policy_ok(int32_t policy) { return policy == WH_POLICY_GREEDY || policy == WH_POLICY_RANDOM; }
+inline bool p_ok(float p) { return p >= 0.0f && p <= 1.0f; }   // (a NaN fails both comparisons)
+inline bool phase_ok(int32_t phase) { return phase >= WH_PHASE_ALL && phase <= WH_PHASE_REGEN; }
+inline bool lanes_ok(int32_t lanes) { return lanes == 1 || lanes == WH_WIDE_LANES; }
+// episode bins are folded from the per-env return accumulator: bins without it are refused
+inline bool stats_ok(const wh_episode_stats* st) {
+  return !st || st->episode_return || (!st->return_sum && !st->episodes && !st->return_min && !st->return_max);
+}
+// entries per order row: 0 = agent_slots, else 1 .. 4 * agent_slots (every key form of every agent,
+// core.py:280); -1 = refused
+inline int order_width(const Shape& g, int32_t order_len) {
+  if (order_len == 0) return g.NA;
+  return (order_len >= 1 && order_len <= 4 * g.NA) ? order_len : -1;
+}
+
+// ----------------------------------------------------------------------------- a step-family call
+constexpr int32_t POLICY_EXTERNAL = 0;   // StepCall::policy of the entries that take actions
+constexpr int32_t PHASE_POLICY = 3;      // StepCall::phase of wh_policy: actions out, no transition
+
+struct StepCall {
+  Shape g;
+  int64_t B;
+  uint32_t* state;
+  int32_t lanes;            // 1, or WH_WIDE_LANES (wh_*_wide)
+  int32_t policy;           // POLICY_EXTERNAL, WH_POLICY_GREEDY, WH_POLICY_RANDOM
+  float p;
+  const int32_t* actions;
+  const int32_t* order;
+  int32_t ol;               // entries per order row, resolved (1 .. 4 * NA)
+  const uint8_t* mask;
+  float* rewards;
+  uint8_t* dones;
+  float* returns;
+  const int32_t* regen;
+  int32_t* n_inactive;
+  int32_t* actions_out;     // wh_policy
+  float* obs;
+  void* xfrag;              // wh_vector_step_x
+  uint32_t* state_out;      // wh_sampler_step_to
+  const wh_episode_stats* stats;
+  int32_t steps, phase, autoreset, variable_n;   // (the two flags as 0 / 1)
+  uint64_t seed;
+  int64_t env_offset;
+};
+
+// the head and the tail every family shares
+inline void begin(StepCall* c, int64_t B, const uint32_t* state, uint64_t seed, int64_t env_offset) {
+  *c = StepCall{};
+  c->B = B;
+  c->state = const_cast<uint32_t*>(state);
+  c->lanes = 1;
+  c->steps = 1;
+  c->phase = WH_PHASE_ALL;
+  c->seed = seed;
+  c->env_offset = env_offset;
+}
+inline int finish(StepCall* c, const wh_config* cfg) {
+  const int rc = check_config(cfg, &c->g);
+  if (rc) return rc;
+  if (c->B > 0 && !c->state) return WH_EINVAL;
+  c->ol = order_width(c->g, c->ol);
+  return (c->ol < 0 || c->B < 0) ? WH_EINVAL : WH_OK;
+}
+inline void rollout_options(StepCall* c, int32_t steps, int32_t policy, float p, float* rewards, uint8_t* dones,
+                            const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n) {
+  c->steps = steps;
+  c->policy = policy;
+  c->p = p;
+  c->rewards = rewards;
+  c->dones = dones;
+  c->stats = stats;
+  c->autoreset = autoreset ? 1 : 0;
+  c->variable_n = variable_n ? 1 : 0;
+}
+
+// wh_step, wh_step_wide (order = NULL, the whole step)
+inline int step_call(StepCall* c, const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
+                     const int32_t* order, int32_t order_len, float* rewards, uint8_t* dones, const int32_t* regen,
+                     int32_t* n_inactive, int32_t phase, uint64_t seed, int64_t env_offset, int32_t lanes) {
+  if (!lanes_ok(lanes) || !phase_ok(phase)) return WH_EINVAL;
+  if (B > 0 && phase != WH_PHASE_REGEN && !actions) return WH_EINVAL;
+  begin(c, B, state, seed, env_offset);
+  c->lanes = lanes;
+  c->actions = actions;
+  c->order = order;
+  c->ol = order_len;
+  c->rewards = rewards;
+  c->dones = dones;
+  c->regen = regen;
+  c->n_inactive = n_inactive;
+  c->phase = phase;
+  return finish(c, cfg);
+}
+
+// wh_policy
+inline int policy_call(StepCall* c, const wh_config* cfg, int64_t B, const uint32_t* state, int32_t policy, float p,
+                       int32_t* actions, uint64_t seed, int64_t env_offset) {
+  if (!policy_ok(policy) || (B > 0 && !actions) || !p_ok(p)) return WH_EINVAL;
+  begin(c, B, state, seed, env_offset);
+  c->policy = policy;
+  c->p = p;
+  c->actions_out = actions;
+  c->steps = 0;
+  c->phase = PHASE_POLICY;
+  return finish(c, cfg);
+}
+
+// wh_rollout, wh_rollout_prepare, wh_rollout_wide
+inline int rollout_call(StepCall* c, const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy,
+                        float p, float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
+                        int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes) {
+  if (!lanes_ok(lanes) || !policy_ok(policy) || steps < 0 || !p_ok(p) || !stats_ok(stats)) return WH_EINVAL;
+  begin(c, B, state, seed, env_offset);
+  rollout_options(c, steps, policy, p, rewards, dones, stats, autoreset, variable_n);
+  c->lanes = lanes;
+  c->returns = returns;
+  return finish(c, cfg);
+}
+
+// wh_vector_step, wh_vector_step_x (rows to `xfrag`, required), wh_vector_step_wide (order = NULL)
+inline int vector_step_call(StepCall* c, const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
+                            const int32_t* order, int32_t order_len, const uint8_t* mask, float* rewards,
+                            uint8_t* dones, float* obs, void* xfrag, bool to_xfrag, const wh_episode_stats* stats,
+                            int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes) {
+  if (!lanes_ok(lanes) || (B > 0 && !actions)) return WH_EINVAL;
+  if (to_xfrag && ((B > 0 && !xfrag) || (uintptr_t)xfrag % 16 != 0)) return WH_EINVAL;
+  if (!stats_ok(stats)) return WH_EINVAL;
+  begin(c, B, state, seed, env_offset);
+  rollout_options(c, 1, POLICY_EXTERNAL, 0.0f, rewards, dones, stats, autoreset, variable_n);
+  c->lanes = lanes;
+  c->actions = actions;
+  c->order = order;
+  c->ol = order_len;
+  c->mask = mask;
+  c->obs = obs;
+  c->xfrag = xfrag;
+  return finish(c, cfg);
+}
+
+// wh_sampler_step, wh_sampler_step_to (the state written to `state_out`, required)
+inline int sampler_step_call(StepCall* c, const wh_config* cfg, int64_t B, const uint32_t* state, uint32_t* state_out,
+                             bool to_state_out, int32_t policy, float p, float* rewards, uint8_t* dones, float* obs,
+                             const wh_episode_stats* stats, int32_t variable_n, uint64_t seed, int64_t env_offset) {
+  if (!policy_ok(policy) || !p_ok(p) || !stats_ok(stats)) return WH_EINVAL;
+  if (to_state_out && B > 0 && !state_out) return WH_EINVAL;
+  begin(c, B, state, seed, env_offset);
+  rollout_options(c, 1, policy, p, rewards, dones, stats, 1, variable_n);
+  c->obs = obs;
+  c->state_out = state_out;
+  return finish(c, cfg);
+}
+
+// wh_sampler_rollout: `steps` sampler steps, the rows of every step kept
+inline int sampler_rollout_call(StepCall* c, const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps,
+                                int32_t policy, float p, float* rewards, uint8_t* dones, float* obs,
+                                const wh_episode_stats* stats, int32_t variable_n, uint64_t seed, int64_t env_offset) {
+  if (!policy_ok(policy) || steps < 0 || !p_ok(p) || !stats_ok(stats)) return WH_EINVAL;
+  if (B > 0 && steps > 0 && !obs) return WH_EINVAL;
+  begin(c, B, state, seed, env_offset);
+  rollout_options(c, steps, policy, p, rewards, dones, stats, 1, variable_n);
+  c->obs = obs;
+  return finish(c, cfg);
+}
+
+}  // namespace wh_abi

@@ -16,12 +16,18 @@
 // two engines with a plain copy, and the philox draws follow the device's stream layout word for
 // word: a CPU rollout equals a GPU rollout bit for bit (tests/test_host_engine.py, tests/test_gpu_host_engine.py).
 // Envs are independent; batches of many envs are split over host threads (OpenMP).
+//
+// Which calls are refused is not this engine's business: the config checks, the option rules and a
+// step-family call reduced to one struct come from abi_args.h, which the gfx950 library uses too, so
+// both refuse the same calls with the same codes (tests/test_abi_refusals.py).  What is written here
+// is the transition, this engine's own limits (make_geo) and one per-env driver for the step family.
 #include <stdint.h>
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "abi_args.h"
 #include "warehouse_amd.h"
 
 namespace {
@@ -33,33 +39,20 @@ constexpr int kMaxD = 32;
 enum Purpose : uint32_t { PUR_RESET = 1, PUR_REGEN = 2, PUR_POLICY = 3, PUR_RANDOM = 4 };
 
 // ----------------------------------------------------------------------------- geometry
-struct Geo {
-  int D, R, NR, NA, P, DP, T, W, NV, words, L;
-  int racks[WH_MAX_RACKS];
+struct Geo : wh_abi::Shape {   // a valid config's sizes (abi_args.h) and this engine's tables
+  int NV;
   int8_t cell[kMaxD][kMaxD];   // [x][y]: pickup index, -1 for other cells
   int px[kMaxP], py[kMaxP];    // pickup point cells (core.py:171-175)
   int dxc[kMaxP], dyc[kMaxP];  // delivery point cells (core.py:178-188)
   int vx[kMaxD * kMaxD], vy[kMaxD * kMaxD];   // spawn cells: interior, not a pickup, ascending (x, y)
 };
 
-int make_geo(const wh_config* c, Geo* g) {
-  if (!c) return WH_EINVAL;
-  g->D = c->area_dimension;
-  g->R = c->num_requests;
-  g->NR = c->num_racks;
-  g->NA = c->agent_slots;
-  g->T = c->episode_duration;
-  g->W = c->pickup_wait_duration;
-  if (g->NR < 1 || g->NR > WH_MAX_RACKS || g->D < 5 || g->D > kMaxD) return WH_EINVAL;
-  g->P = 4 * g->NR * g->NR;
-  g->DP = 4 * (g->D - 4);
-  if (g->NA < 1 || g->NA > g->R || g->R > g->P || g->R > g->DP) return WH_EINVAL;
-  if (g->W < 1 || g->W > 255 || g->T < 0) return WH_EINVAL;
+// The tables of a valid config; what this engine cannot run (more points or agents than its 64-bit
+// sets hold, racks that overlap) is WH_ENOTSUP.
+int make_geo(const wh_abi::Shape& shape, Geo* g) {
+  static_cast<wh_abi::Shape&>(*g) = shape;
+  static_assert(kMaxD >= 32, "the ABI's largest area");
   if (g->P > kMaxP || g->DP > kMaxP || g->NA > kMaxA) return WH_ENOTSUP;
-  for (int i = 0; i < g->NR; ++i) {
-    g->racks[i] = c->racks[i];
-    if (c->racks[i] < 2 || c->racks[i] > g->D - 2) return WH_ENOTSUP;   // pickups must be interior
-  }
   memset(g->cell, -1, sizeof(g->cell));
   // pickup points: for x in racks, for y in racks: (x-1, y-1), (x, y-1), (x-1, y), (x, y)
   int j = 0;
@@ -86,9 +79,13 @@ int make_geo(const wh_config* c, Geo* g) {
         g->vy[g->NV] = y;
         ++g->NV;
       }
-  g->words = 2 + g->NA + 2 * (g->P / 4);
-  g->L = 9 * g->R + 1;
   return WH_OK;
+}
+
+int make_geo(const wh_config* c, Geo* g) {
+  wh_abi::Shape shape;
+  const int rc = wh_abi::check_config(c, &shape);
+  return rc ? rc : make_geo(shape, g);
 }
 
 // delivery cell -> delivery index (the inverse of the table above)
@@ -520,17 +517,69 @@ void fold_episode(const wh_episode_stats* st, uint32_t n, uint32_t ret) {
   }
 }
 
-bool stats_ok(const wh_episode_stats* st) {
-  return !st || st->episode_return || (!st->return_sum && !st->episodes && !st->return_min && !st->return_max);
-}
-
 uint32_t keys_lo(uint64_t seed) { return (uint32_t)(seed & 0xFFFFFFFFu); }
 uint32_t keys_hi(uint64_t seed) { return (uint32_t)(seed >> 32); }
 
-// order rows: 0 = agent_slots entries per env, else 1 .. 4 * agent_slots
-int order_width(const Geo& g, int32_t order_len) {
-  if (order_len == 0) return g.NA;
-  return (order_len >= 1 && order_len <= 4 * g.NA) ? order_len : -1;
+// ----------------------------------------------------------------------------- the step family
+// One env of a checked step-family call (abi_args.h): c.steps times [policy ->] step -> rewards /
+// dones -> episode-return fold -> auto-reset on an unmasked env, then its rows.  wh_step (phases,
+// injected regeneration draws), wh_rollout (a policy, K steps, returns), wh_vector_step (a mask,
+// rows) and wh_sampler_step (a policy, rows) are this with the options each one sets.
+void drive_env(const Geo& g, const wh_abi::StepCall& c, int64_t e) {
+  const int64_t B = c.B;
+  const uint32_t k0 = keys_lo(c.seed), k1 = keys_hi(c.seed), gid = (uint32_t)(c.env_offset + e);
+  Env s;
+  load(g, c.state, B, e, s);
+  if (!c.mask || c.mask[e]) {
+    const bool st = c.stats && c.stats->episode_return;
+    uint32_t epr = st ? c.stats->episode_return[e] : 0u;
+    float ret = 0.0f;
+    int32_t acts[kMaxA];
+    for (int k = 0; k < c.steps; ++k) {
+      const int32_t* a = c.actions ? c.actions + e * g.NA : nullptr;
+      if (c.policy != wh_abi::POLICY_EXTERNAL) {
+        policy_env(g, s, c.policy, c.p, k0, k1, gid, acts);
+        a = acts;
+      }
+      const StepOut o = step_env(g, s, a, c.order ? c.order + e * c.ol : nullptr, c.ol,
+                                 c.regen ? c.regen + e * 2 * g.R : nullptr, k0, k1, gid, c.phase);
+      const int64_t row = (int64_t)k * B + e;
+      float r = 0.0f;
+      for (int i = 0; i < g.NA; ++i) r += o.rew[i];
+      if (c.phase != WH_PHASE_REGEN) {
+        if (c.rewards)
+          for (int i = 0; i < g.NA; ++i) c.rewards[row * g.NA + i] = o.rew[i];
+        if (c.dones) c.dones[row] = o.done ? 1 : 0;
+      }
+      if (c.phase == WH_PHASE_PRE_REGEN && c.n_inactive) c.n_inactive[e] = o.nin;
+      ret += r;
+      if (st) {
+        epr += (uint32_t)r;
+        if (o.done) {
+          fold_episode(c.stats, s.n, epr);
+          epr = 0;
+        }
+      }
+      if (o.done && c.autoreset) reset_philox(g, s, k0, k1, gid, c.variable_n != 0);
+    }
+    if (c.returns) c.returns[e] += ret;
+    if (st) c.stats->episode_return[e] = epr;
+    store(g, c.state, B, e, s);
+  }
+  if (c.obs) observe_env(g, s, c.obs + e * g.NA * g.L);
+}
+
+// every env of the call, over host threads from `par_min` envs on
+void run_envs(const Geo& g, const wh_abi::StepCall& c, int64_t par_min) {
+#pragma omp parallel for schedule(static) if (c.B >= par_min)
+  for (int64_t e = 0; e < c.B; ++e) drive_env(g, c, e);
+}
+
+int run_call(int rc, const wh_abi::StepCall& c, int64_t par_min = 1024) {
+  Geo g;
+  if (rc || (rc = make_geo(c.g, &g))) return rc;
+  run_envs(g, c, par_min);
+  return WH_OK;
 }
 
 }  // namespace
@@ -641,37 +690,13 @@ int wh_reset(const wh_config* cfg, int64_t B, uint32_t* state, const uint8_t* ma
 
 int wh_step(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, const int32_t* order,
             int32_t order_len, float* rewards, uint8_t* dones, const int32_t* regen, int32_t* n_inactive,
-            int32_t phase, uint64_t seed, int64_t env_offset, void* stream) {
-  (void)stream;
-  if (phase < WH_PHASE_ALL || phase > WH_PHASE_REGEN) return WH_EINVAL;
-  if (B > 0 && phase != WH_PHASE_REGEN && !actions) return WH_EINVAL;
-  Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  const int ol = order_width(g, order_len);
-  if (B < 0 || ol < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  if (!state) return WH_EINVAL;
-#pragma omp parallel for schedule(static) if (B >= 1024)
-  for (int64_t e = 0; e < B; ++e) {
-    Env s;
-    load(g, state, B, e, s);
-    const StepOut o = step_env(g, s, actions ? actions + e * g.NA : nullptr, order ? order + e * ol : nullptr, ol,
-                               regen ? regen + e * 2 * g.R : nullptr, keys_lo(seed), keys_hi(seed),
-                               (uint32_t)(env_offset + e), phase);
-    if (phase != WH_PHASE_REGEN) {
-      if (rewards)
-        for (int i = 0; i < g.NA; ++i) rewards[e * g.NA + i] = o.rew[i];
-      if (dones) dones[e] = o.done ? 1 : 0;
-    }
-    if (phase == WH_PHASE_PRE_REGEN && n_inactive) n_inactive[e] = o.nin;
-    store(g, state, B, e, s);
-  }
-  return WH_OK;
+            int32_t phase, uint64_t seed, int64_t env_offset, void*) {
+  wh_abi::StepCall c;
+  return run_call(wh_abi::step_call(&c, cfg, B, state, actions, order, order_len, rewards, dones, regen, n_inactive,
+                                    phase, seed, env_offset, 1), c);
 }
 
-int wh_observe(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void* stream) {
-  (void)stream;
+int wh_observe(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void*) {
   Geo g;
   const int rc = make_geo(cfg, &g);
   if (rc) return rc;
@@ -687,22 +712,12 @@ int wh_observe(const wh_config* cfg, int64_t B, const uint32_t* state, float* ob
   return WH_OK;
 }
 
-int wh_observe_x(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void* xfrag, void* stream) {
-  (void)cfg, (void)B, (void)state, (void)obs, (void)xfrag, (void)stream;
-  return WH_ENOTSUP;   // the policy network's MFMA operand: a device format
-}
-
 int wh_policy(const wh_config* cfg, int64_t B, const uint32_t* state, int32_t policy, float p, int32_t* actions,
-              uint64_t seed, int64_t env_offset, void* stream) {
-  (void)stream;
-  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || (B > 0 && !actions)) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f)) return WH_EINVAL;
+              uint64_t seed, int64_t env_offset, void*) {
+  wh_abi::StepCall c;
   Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  if (!state) return WH_EINVAL;
+  int rc = wh_abi::policy_call(&c, cfg, B, state, policy, p, actions, seed, env_offset);
+  if (rc || (rc = make_geo(c.g, &g))) return rc;
 #pragma omp parallel for schedule(static) if (B >= 1024)
   for (int64_t e = 0; e < B; ++e) {
     Env s;
@@ -714,209 +729,78 @@ int wh_policy(const wh_config* cfg, int64_t B, const uint32_t* state, int32_t po
 
 int wh_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
                float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats, int32_t autoreset,
-               int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream) {
-  (void)stream;
-  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || steps < 0) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  if (!state) return WH_EINVAL;
-  const bool st = stats && stats->episode_return;
-#pragma omp parallel for schedule(static) if (B >= 256)
-  for (int64_t e = 0; e < B; ++e) {
-    Env s;
-    load(g, state, B, e, s);
-    const uint32_t gid = (uint32_t)(env_offset + e);
-    uint32_t epr = st ? stats->episode_return[e] : 0u;
-    float ret = 0.0f;
-    int32_t acts[kMaxA];
-    for (int k = 0; k < steps; ++k) {
-      policy_env(g, s, policy, p, keys_lo(seed), keys_hi(seed), gid, acts);
-      const StepOut o = step_env(g, s, acts, nullptr, 0, nullptr, keys_lo(seed), keys_hi(seed), gid, WH_PHASE_ALL);
-      if (rewards)
-        for (int i = 0; i < g.NA; ++i) rewards[((int64_t)k * B + e) * g.NA + i] = o.rew[i];
-      if (dones) dones[(int64_t)k * B + e] = o.done ? 1 : 0;
-      float r = 0.0f;
-      for (int i = 0; i < g.NA; ++i) r += o.rew[i];
-      ret += r;
-      if (st) {
-        epr += (uint32_t)r;
-        if (o.done) {
-          fold_episode(stats, s.n, epr);
-          epr = 0;
-        }
-      }
-      if (o.done && autoreset) reset_philox(g, s, keys_lo(seed), keys_hi(seed), gid, variable_n != 0);
-    }
-    if (returns) returns[e] += ret;
-    if (st) stats->episode_return[e] = epr;
-    store(g, state, B, e, s);
-  }
-  return WH_OK;
+               int32_t variable_n, uint64_t seed, int64_t env_offset, void*) {
+  wh_abi::StepCall c;
+  return run_call(wh_abi::rollout_call(&c, cfg, B, state, steps, policy, p, rewards, dones, returns, stats, autoreset,
+                                       variable_n, seed, env_offset, 1), c, 256);
 }
 
 int wh_vector_step(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, const int32_t* order,
                    int32_t order_len, const uint8_t* mask, float* rewards, uint8_t* dones, float* obs,
                    const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
-                   int64_t env_offset, void* stream) {
-  (void)stream;
-  if (B > 0 && !actions) return WH_EINVAL;
-  if (!stats_ok(stats)) return WH_EINVAL;
+                   int64_t env_offset, void*) {
+  wh_abi::StepCall c;
+  return run_call(wh_abi::vector_step_call(&c, cfg, B, state, actions, order, order_len, mask, rewards, dones, obs,
+                                           nullptr, false, stats, autoreset, variable_n, seed, env_offset, 1), c);
+}
+
+// policy + vector step per env (every env stepped, auto-reset)
+int wh_sampler_step(const wh_config* cfg, int64_t B, uint32_t* state, int32_t policy, float p, float* rewards,
+                    uint8_t* dones, float* obs, const wh_episode_stats* stats, int32_t variable_n, uint64_t seed,
+                    int64_t env_offset, void*) {
+  wh_abi::StepCall c;
+  return run_call(wh_abi::sampler_step_call(&c, cfg, B, state, nullptr, false, policy, p, rewards, dones, obs, stats,
+                                            variable_n, seed, env_offset), c);
+}
+
+// `steps` sampler steps over the whole batch, the rows of every step kept
+int wh_sampler_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
+                       float* rewards, uint8_t* dones, float* obs, const wh_episode_stats* stats, int32_t variable_n,
+                       uint64_t seed, int64_t env_offset, void*) {
+  wh_abi::StepCall c;
   Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  const int ol = order_width(g, order_len);
-  if (B < 0 || ol < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  if (!state) return WH_EINVAL;
-  const bool st = stats && stats->episode_return;
-#pragma omp parallel for schedule(static) if (B >= 1024)
-  for (int64_t e = 0; e < B; ++e) {
-    Env s;
-    load(g, state, B, e, s);
-    if (!mask || mask[e]) {
-      const uint32_t gid = (uint32_t)(env_offset + e);
-      const StepOut o = step_env(g, s, actions + e * g.NA, order ? order + e * ol : nullptr, ol, nullptr, keys_lo(seed),
-                                 keys_hi(seed), gid, WH_PHASE_ALL);
-      if (rewards)
-        for (int i = 0; i < g.NA; ++i) rewards[e * g.NA + i] = o.rew[i];
-      if (dones) dones[e] = o.done ? 1 : 0;
-      if (st) {
-        float r = 0.0f;
-        for (int i = 0; i < g.NA; ++i) r += o.rew[i];
-        uint32_t epr = stats->episode_return[e] + (uint32_t)r;
-        if (o.done) {
-          fold_episode(stats, s.n, epr);
-          epr = 0;
-        }
-        stats->episode_return[e] = epr;
-      }
-      if (o.done && autoreset) reset_philox(g, s, keys_lo(seed), keys_hi(seed), gid, variable_n != 0);
-      store(g, state, B, e, s);
-    }
-    if (obs) observe_env(g, s, obs + e * g.NA * g.L);
+  int rc = wh_abi::sampler_rollout_call(&c, cfg, B, state, steps, policy, p, rewards, dones, obs, stats, variable_n,
+                                        seed, env_offset);
+  if (rc || (rc = make_geo(c.g, &g))) return rc;
+  c.steps = 1;
+  for (int32_t k = 0; k < steps; ++k) {
+    run_envs(g, c, 1024);
+    if (c.rewards) c.rewards += B * g.NA;
+    if (c.dones) c.dones += B;
+    if (c.obs) c.obs += B * g.NA * g.L;
   }
   return WH_OK;
 }
 
-int wh_vector_step_x(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, const int32_t* order,
-                     int32_t order_len, const uint8_t* mask, float* rewards, uint8_t* dones, void* xfrag,
-                     const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
-                     int64_t env_offset, void* stream) {
-  (void)cfg, (void)B, (void)state, (void)actions, (void)order, (void)order_len, (void)mask, (void)rewards,
-      (void)dones, (void)xfrag, (void)stats, (void)autoreset, (void)variable_n, (void)seed, (void)env_offset,
-      (void)stream;
-  return WH_ENOTSUP;
-}
-
-int wh_sampler_step(const wh_config* cfg, int64_t B, uint32_t* state, int32_t policy, float p, float* rewards,
-                    uint8_t* dones, float* obs, const wh_episode_stats* stats, int32_t variable_n, uint64_t seed,
-                    int64_t env_offset, void* stream) {
-  if (policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  std::vector<int32_t> acts((size_t)B * g.NA);
-  int r = wh_policy(cfg, B, state, policy, p, acts.data(), seed, env_offset, stream);
-  if (r) return r;
-  return wh_vector_step(cfg, B, state, acts.data(), nullptr, 0, nullptr, rewards, dones, obs, stats, 1, variable_n,
-                        seed, env_offset, stream);
-}
-
-int wh_sampler_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
-                       float* rewards, uint8_t* dones, float* obs, const wh_episode_stats* stats, int32_t variable_n,
-                       uint64_t seed, int64_t env_offset, void* stream) {
-  if (steps < 0) return WH_EINVAL;
-  if (B > 0 && steps > 0 && !obs) return WH_EINVAL;
-  Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  int r = WH_OK;
-  for (int32_t k = 0; k < steps && r == WH_OK; ++k)
-    r = wh_sampler_step(cfg, B, state, policy, p, rewards ? rewards + (int64_t)k * B * g.NA : nullptr,
-                        dones ? dones + (int64_t)k * B : nullptr, obs + (int64_t)k * B * g.NA * g.L, stats, variable_n,
-                        seed, env_offset, stream);
-  return r;
-}
-
-int wh_sampler_step_to(const wh_config* cfg, int64_t B, const uint32_t* state_in, uint32_t* state_out, int32_t policy,
-                       float p, float* rewards, uint8_t* dones, const wh_episode_stats* stats, int32_t variable_n,
-                       uint64_t seed, int64_t env_offset, void* stream) {
-  (void)cfg, (void)B, (void)state_in, (void)state_out, (void)policy, (void)p, (void)rewards, (void)dones, (void)stats,
-      (void)variable_n, (void)seed, (void)env_offset, (void)stream;
-  return WH_ENOTSUP;   // a two-stream device pipeline
-}
-
-int wh_rollout_prepare(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
-                       float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats, int32_t autoreset,
-                       int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream, wh_launch** out) {
-  (void)cfg, (void)B, (void)state, (void)steps, (void)policy, (void)p, (void)rewards, (void)dones, (void)returns,
-      (void)stats, (void)autoreset, (void)variable_n, (void)seed, (void)env_offset, (void)stream;
+// ---- what the CPU has no use for: the policy network and its fragment operand (device formats),
+// the two-stream sampler step, prepared launches, assert-mode counters, and the 16-lanes-per-env
+// form (csrc/step_wide.h: the host engine has no lanes)
+int wh_observe_x(const wh_config*, int64_t, const uint32_t*, float*, void*, void*) { return WH_ENOTSUP; }
+int wh_vector_step_x(const wh_config*, int64_t, uint32_t*, const int32_t*, const int32_t*, int32_t, const uint8_t*,
+                     float*, uint8_t*, void*, const wh_episode_stats*, int32_t, int32_t, uint64_t, int64_t, void*) { return WH_ENOTSUP; }
+int wh_sampler_step_to(const wh_config*, int64_t, const uint32_t*, uint32_t*, int32_t, float, float*, uint8_t*,
+                       const wh_episode_stats*, int32_t, uint64_t, int64_t, void*) { return WH_ENOTSUP; }
+int wh_rollout_prepare(const wh_config*, int64_t, uint32_t*, int32_t, int32_t, float, float*, uint8_t*, float*,
+                       const wh_episode_stats*, int32_t, int32_t, uint64_t, int64_t, void*, wh_launch** out) {
   if (out) *out = nullptr;
-  return WH_ENOTSUP;   // prepared device launches
+  return WH_ENOTSUP;
 }
-int wh_launch_run(const wh_launch* launch) { return launch ? WH_EINVAL : WH_EINVAL; }
-int wh_launch_run_timed(const wh_launch* launch, void* start_event, void* stop_event) {
-  (void)launch, (void)start_event, (void)stop_event;
-  return WH_EINVAL;
-}
+int wh_launch_run(const wh_launch*) { return WH_EINVAL; }   // (no handle is ever live here)
+int wh_launch_run_timed(const wh_launch*, void*, void*) { return WH_EINVAL; }
 int wh_launch_free(wh_launch* launch) { return launch ? WH_EINVAL : WH_OK; }
-
-int wh_mlp_query(const wh_mlp_desc* d, int64_t* packed_bytes) {
-  (void)d, (void)packed_bytes;
-  return WH_ENOTSUP;   // the policy network runs on the device only
-}
-int wh_mlp_pack(const wh_mlp_desc* d, const float* w0, const float* b0, const float* w1, const float* b1,
-                const float* w2, const float* b2, void* packed) {
-  (void)d, (void)w0, (void)b0, (void)w1, (void)b1, (void)w2, (void)b2, (void)packed;
-  return WH_ENOTSUP;
-}
-int wh_mlp_forward(const wh_mlp_desc* d, const void* packed, int64_t rows, const float* obs, float* logits,
-                   int32_t* actions, int32_t explore, uint64_t seed, uint32_t step, void* stream) {
-  (void)d, (void)packed, (void)rows, (void)obs, (void)logits, (void)actions, (void)explore, (void)seed, (void)step,
-      (void)stream;
-  return WH_ENOTSUP;
-}
-int wh_mlp_forward_x(const wh_mlp_desc* d, const void* packed, int64_t rows, const void* xfrag, float* logits,
-                     int32_t* actions, int32_t explore, uint64_t seed, uint32_t step, void* stream) {
-  (void)d, (void)packed, (void)rows, (void)xfrag, (void)logits, (void)actions, (void)explore, (void)seed, (void)step,
-      (void)stream;
-  return WH_ENOTSUP;
-}
-int wh_check_read(uint64_t* out, int32_t clear) {
-  (void)out, (void)clear;
-  return WH_ENOTSUP;
-}
-
-// The 16-lanes-per-env form is a device execution form (csrc/step_wide.h): the host engine has no lanes.
-int wh_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, float* rewards,
-                 uint8_t* dones, const int32_t* regen, int32_t* n_inactive, uint64_t seed, int64_t env_offset,
-                 int32_t lanes, void* stream) {
-  (void)cfg, (void)B, (void)state, (void)actions, (void)rewards, (void)dones, (void)regen, (void)n_inactive,
-      (void)seed, (void)env_offset, (void)lanes, (void)stream;
-  return WH_ENOTSUP;
-}
-int wh_rollout_wide(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
-                    float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
-                    int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes,
-                    void* stream) {
-  (void)cfg, (void)B, (void)state, (void)steps, (void)policy, (void)p, (void)rewards, (void)dones, (void)returns,
-      (void)stats, (void)autoreset, (void)variable_n, (void)seed, (void)env_offset, (void)lanes, (void)stream;
-  return WH_ENOTSUP;
-}
-int wh_vector_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
-                        const uint8_t* mask, float* rewards, uint8_t* dones, float* obs,
-                        const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
-                        int64_t env_offset, int32_t lanes, void* stream) {
-  (void)cfg, (void)B, (void)state, (void)actions, (void)mask, (void)rewards, (void)dones, (void)obs, (void)stats,
-      (void)autoreset, (void)variable_n, (void)seed, (void)env_offset, (void)lanes, (void)stream;
-  return WH_ENOTSUP;
-}
+int wh_mlp_query(const wh_mlp_desc*, int64_t*) { return WH_ENOTSUP; }
+int wh_mlp_pack(const wh_mlp_desc*, const float*, const float*, const float*, const float*, const float*,
+                const float*, void*) { return WH_ENOTSUP; }
+int wh_mlp_forward(const wh_mlp_desc*, const void*, int64_t, const float*, float*, int32_t*, int32_t, uint64_t,
+                   uint32_t, void*) { return WH_ENOTSUP; }
+int wh_mlp_forward_x(const wh_mlp_desc*, const void*, int64_t, const void*, float*, int32_t*, int32_t, uint64_t,
+                     uint32_t, void*) { return WH_ENOTSUP; }
+int wh_check_read(uint64_t*, int32_t) { return WH_ENOTSUP; }
+int wh_step_wide(const wh_config*, int64_t, uint32_t*, const int32_t*, float*, uint8_t*, const int32_t*, int32_t*,
+                 uint64_t, int64_t, int32_t, void*) { return WH_ENOTSUP; }
+int wh_rollout_wide(const wh_config*, int64_t, uint32_t*, int32_t, int32_t, float, float*, uint8_t*, float*,
+                    const wh_episode_stats*, int32_t, int32_t, uint64_t, int64_t, int32_t, void*) { return WH_ENOTSUP; }
+int wh_vector_step_wide(const wh_config*, int64_t, uint32_t*, const int32_t*, const uint8_t*, float*, uint8_t*, float*,
+                        const wh_episode_stats*, int32_t, int32_t, uint64_t, int64_t, int32_t, void*) { return WH_ENOTSUP; }
 
 }  // extern "C"

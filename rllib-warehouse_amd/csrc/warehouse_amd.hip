@@ -19,6 +19,9 @@
 //    target bytes core.py:327-329), laid out [word][lane] so every lane hits its own bank, and no
 //    data-dependent branches: LDS side effects are predicated through neutral operands.
 //  * Counter-based Philox streams (no RNG state in HBM) or injected draws (parity mode).
+// The host side (from "host side" down) owns the device tables, the kernel registry and the launch
+// decisions; which arguments a call is refused for is written in abi_args.h, shared with the host
+// engine (host_engine.cpp), and every step-family entry point goes through it.
 #include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
@@ -31,6 +34,7 @@
 #include <string.h>
 #include <vector>
 
+#include "abi_args.h"
 #include "philox.h"
 #include "warehouse_amd.h"
 
@@ -2656,30 +2660,13 @@ __global__ __launch_bounds__(BT) void k_unpack(PackParams a) {
 // ----------------------------------------------------------------------------- host side
 int hip_err(hipError_t e) { return e == hipSuccess ? WH_OK : WH_EHIP + (int)e; }
 
-struct Geometry {
-  int D, R, NR, NA, P, DP, T, W;
-  int racks[WH_MAX_RACKS];
-};
-
-int validate(const wh_config* c, Geometry* g) {
-  if (!c) return WH_EINVAL;
-  g->D = c->area_dimension;
-  g->R = c->num_requests;
-  g->NR = c->num_racks;
-  g->NA = c->agent_slots;
-  g->T = c->episode_duration;
-  g->W = c->pickup_wait_duration;
-  if (g->NR < 1 || g->NR > WH_MAX_RACKS || g->D < 5 || g->D > 32) return WH_EINVAL;
-  g->P = 4 * g->NR * g->NR;
-  g->DP = 4 * (g->D - 4);
-  if (g->NA < 1 || g->NA > g->R || g->R > g->P || g->R > g->DP) return WH_EINVAL;
-  if (g->W < 1 || g->W > 255 || g->T < 0) return WH_EINVAL;
-  for (int i = 0; i < g->NR; ++i) {
-    g->racks[i] = c->racks[i];
-    if (c->racks[i] < 2 || c->racks[i] > g->D - 2) return WH_ENOTSUP;  // pickups must be interior
-  }
-  return WH_OK;
-}
+// Which calls are refused, and a step-family call reduced to one struct, are the ABI's own rules
+// (abi_args.h, shared with the host engine); what follows is what this back end adds: the device
+// tables, the kernel instances, and which of them a call launches.
+using Geometry = wh_abi::Shape;
+using wh_abi::StepCall;
+static_assert(wh_abi::POLICY_EXTERNAL == POL_EXTERNAL && WH_POLICY_GREEDY == POL_GREEDY && WH_POLICY_RANDOM == POL_RANDOM &&
+              wh_abi::PHASE_POLICY == PH_POLICY && WH_PHASE_ALL == PH_ALL, "StepCall carries the kernels' codes");
 
 // Host copy of the per-workgroup tables, same layout as TableLayout (core.py:170-199):
 //   cell  [256*D] u8 : (x | y << 8) -> pickup index + 1, 0 = not a pickup cell
@@ -2896,7 +2883,7 @@ bool fused_ok(void (*kern)(StepParams, float*)) {
 // with the fused instance free of scratch); Small-4 13.2 vs 15.1, Medium-8 34.7 vs 40.3
 // (profiles/r05_step3_ab.txt).  So configurations with more than WH_FUSE_ROWS_MAX bytes of rows per
 // env take the two launches.
-bool fuse_rows(const Geometry& g) { return 4 * g.NA * (9 * g.R + 1) <= WH_FUSE_ROWS_MAX; }
+bool fuse_rows(const Geometry& g) { return 4 * g.NA * g.L <= WH_FUSE_ROWS_MAX; }
 
 const Kernels* pick(const Geometry& g) {
   const Kernels* best = nullptr;
@@ -2906,16 +2893,21 @@ const Kernels* pick(const Geometry& g) {
   return best;
 }
 
-int prepare(const wh_config* cfg, int64_t B, void* stream, Geometry* g, const Kernels** kk,
-            const uint32_t** tab) {
-  int rc = validate(cfg, g);
-  if (rc) return rc;
-  if (B < 0) return WH_EINVAL;
-  *kk = pick(*g);
+// The kernel instance of a valid geometry and, for a batch that launches, its device tables.
+int locate(const Geometry& g, int64_t B, void* stream, const Kernels** kk, const uint32_t** tab) {
+  *kk = pick(g);
   if (!*kk) return WH_ENOTSUP;
   *tab = nullptr;
   if (B == 0) return WH_OK;   // an empty batch launches nothing: no device, no tables
-  return device_tables(*g, (*kk)->tblw, (hipStream_t)stream, tab);
+  return device_tables(g, (*kk)->tblw, (hipStream_t)stream, tab);
+}
+
+int prepare(const wh_config* cfg, int64_t B, void* stream, Geometry* g, const Kernels** kk,
+            const uint32_t** tab) {
+  int rc = wh_abi::check_config(cfg, g);
+  if (rc) return rc;
+  if (B < 0) return WH_EINVAL;
+  return locate(*g, B, stream, kk, tab);
 }
 
 inline dim3 grid_for(int64_t B) { return dim3((unsigned)((B + BT - 1) / BT)); }
@@ -2973,15 +2965,15 @@ int wh_check_read(uint64_t* out, int32_t clear) {
 
 int wh_query(const wh_config* cfg, wh_layout* out) {
   Geometry g;
-  int rc = validate(cfg, &g);
+  int rc = wh_abi::check_config(cfg, &g);
   if (rc) return rc;
   const Kernels* k = pick(g);
   if (!k) return WH_ENOTSUP;
   if (out) {
-    out->words_per_env = 2 + g.NA + 2 * (g.P / 4);
+    out->words_per_env = g.words;
     out->num_pickups = g.P;
     out->num_deliveries = g.DP;
-    out->obs_len = 9 * g.R + 1;
+    out->obs_len = g.L;
     out->kernel_agents = k->NAM;
   }
   return WH_OK;
@@ -2992,7 +2984,7 @@ int wh_pack(const wh_config* cfg, int64_t B, const int32_t* pos, const int32_t* 
             const int32_t* n, const uint8_t* fresh, const uint32_t* episode, uint32_t* state,
             void* stream) {
   Geometry g;
-  int rc = validate(cfg, &g);
+  int rc = wh_abi::check_config(cfg, &g);
   if (rc) return rc;
   if (B == 0) return WH_OK;
   if (B < 0 || !pos || !agent_target || !pickup_target || !pickup_timer || !t || !n || !fresh ||
@@ -3010,7 +3002,7 @@ int wh_unpack(const wh_config* cfg, int64_t B, const uint32_t* state, int32_t* p
               int32_t* agent_target, int32_t* pickup_target, int32_t* pickup_timer, int32_t* t,
               int32_t* n, uint8_t* fresh, uint32_t* episode, void* stream) {
   Geometry g;
-  int rc = validate(cfg, &g);
+  int rc = wh_abi::check_config(cfg, &g);
   if (rc) return rc;
   if (B == 0) return WH_OK;
   if (B < 0 || !pos || !agent_target || !pickup_target || !pickup_timer || !t || !n || !fresh ||
@@ -3045,12 +3037,16 @@ int wh_reset(const wh_config* cfg, int64_t B, uint32_t* state, const uint8_t* ma
 }  // extern "C"
 
 // A step launch with every argument resolved: what launch_step enqueues, and what a prepared
-// launch (wh_rollout_prepare / wh_launch_run) replays without re-validating anything.
+// launch (wh_rollout_prepare / wh_launch_run) replays without re-validating anything.  It keeps the
+// geometry and the kernel instance it was resolved for: the entries that write rows go on from them
+// to a fused step + rows kernel or to k_observe.
 struct wh_launch {
   void (*kern)(StepParams);
   dim3 grid;
   hipStream_t stream;
   StepParams a;
+  Geometry g;
+  const Kernels* k;
 };
 
 // Live handles of wh_rollout_prepare: run / free of anything else (a freed or foreign pointer) is
@@ -3062,42 +3058,63 @@ static bool launch_live(const wh_launch* l) {
   return g_launches.count(l) != 0;
 }
 
-static int resolve_step(const wh_config* cfg, int64_t B, uint32_t* state, int policy, StepParams a,
-                        void* stream, wh_launch* out, int lanes = 1) {
-  Geometry g;
-  const Kernels* k;
-  const uint32_t* tab;
-  // host-side argument checks first (no device needed to refuse them)
-  int rc = validate(cfg, &g);
-  if (rc) return rc;
-  if (policy < 0 || policy > 2) return WH_EINVAL;
-  if (B > 0 && !state) return WH_EINVAL;
-  // order rows: 0 = NA entries, else 1 .. 4 * NA (every key form of every agent, core.py:280)
-  if (a.ol == 0) a.ol = g.NA;
-  if (a.ol < 1 || a.ol > 4 * g.NA) return WH_EINVAL;
-  rc = prepare(cfg, B, stream, &g, &k, &tab);
-  if (rc) return rc;
-  a.state = state;
-  a.B = B;
-  a.na = g.NA;
-  a.T = g.T;
-  a.W = g.W;
-  a.tables = tab;
+// The kernel argument of a checked call (abi_args.h): the one place a StepParams is filled.
+static StepParams step_params(const StepCall& c, const uint32_t* tables) {
+  StepParams a{};
+  a.state = c.state;
+  a.B = c.B;
+  a.na = c.g.NA;
+  a.T = c.g.T;
+  a.W = c.g.W;
+  a.tables = tables;
+  a.actions = c.actions;
+  a.order = c.order;   // non-NULL: the action-dict order path (k_step<..., ORDERED>)
+  a.ol = c.ol;
+  a.rewards = c.rewards;
+  a.dones = c.dones;
+  a.returns = c.returns;
+  a.regen = c.regen;
+  a.n_inactive = c.n_inactive;
+  a.actions_out = c.actions_out;
+  a.p = c.p;
+  a.k0 = (uint32_t)(c.seed & 0xFFFFFFFFu);
+  a.k1 = (uint32_t)(c.seed >> 32);
+  a.env_offset = c.env_offset;
+  a.steps = c.steps;
+  a.phase = c.phase;
+  a.autoreset = c.autoreset;
+  a.variable_n = c.variable_n;
 #ifdef WH_ABLATION
   const char* abl = getenv("WH_ABLATE");   // timing experiments only (tools/ablate.py)
   a.ablate = abl ? atoi(abl) : 0;
 #endif
+  if (c.stats) a.stats = *c.stats;
+  a.mask = c.mask;
+  a.state_out = c.state_out;   // (wh_sampler_step_to: every env is live, each lane stores its whole state)
+  return a;
+}
+
+// The back end's part of a checked call: the kernel instance, the device tables, the step kernel.
+static int resolve_step(const StepCall& c, void* stream, wh_launch* out) {
+  const uint32_t* tab;
+  const int rc = locate(c.g, c.B, stream, &out->k, &tab);
+  if (rc) return rc;
+  const Kernels* k = out->k;
+  const int policy = c.policy;
+  const StepParams a = step_params(c, tab);
   void (*kern)(StepParams) = (a.order != nullptr && policy == POL_EXTERNAL) ? k->step_ordered : k->step[policy];
   // the fused rollout's common case (run_steps_fast); rows of 16 (NAM % 4 == 0) or 8 bytes
   const uintptr_t ralign = (k->NAM % 4 == 0) ? 15u : 7u;
   if (k->step_fast[policy] && a.phase == PH_ALL && a.rewards && a.dones && !a.returns &&
       !a.stats.episode_return && !a.mask && !a.order && !a.regen && !a.n_inactive && a.autoreset &&
-      g.NA == k->NAM && ((uintptr_t)a.rewards & ralign) == 0)
+      c.g.NA == k->NAM && ((uintptr_t)a.rewards & ralign) == 0)
     kern = k->step_fast[policy];
-  out->kern = lanes == WH_WIDE_LANES ? k->step_wide[policy] : kern;
-  out->grid = lanes == WH_WIDE_LANES ? grid_wide(B) : grid_for(B);
+  const bool wide = c.lanes == WH_WIDE_LANES;   // k_step_wide (csrc/step_wide.h): 16 lanes per env
+  out->kern = wide ? k->step_wide[policy] : kern;
+  out->grid = wide ? grid_wide(c.B) : grid_for(c.B);
   out->stream = (hipStream_t)stream;
   out->a = a;
+  out->g = c.g;
   return WH_OK;
 }
 
@@ -3107,11 +3124,98 @@ static int enqueue(const wh_launch& l) {
   return hip_err(hipGetLastError());
 }
 
-static int launch_step(const wh_config* cfg, int64_t B, uint32_t* state, int policy,
-                       StepParams a, void* stream, int lanes = 1) {
+static int launch_step(const StepCall& c, void* stream) {
   wh_launch l;
-  const int rc = resolve_step(cfg, B, state, policy, a, stream, &l, lanes);
+  const int rc = resolve_step(c, stream, &l);
   return rc ? rc : enqueue(l);
+}
+
+// k_observe for B > 0 envs of a resolved geometry: f32 rows to `obs`, the policy network's
+// fragment-order operand to `xfrag` (16-byte aligned), or both.
+static int observe_launch(const Geometry& g, const Kernels* k, const uint32_t* tab, int64_t B, const uint32_t* state,
+                          float* obs, void* xfrag, void* stream) {
+  const int quads = ((g.NA * g.L) % 4 == 0) && ((uintptr_t)obs % 16 == 0);
+  // envs per workgroup (same-box A/Bs, tools/obs_bench.py and tools/sampler_probe.py): f32 rows 64
+  // for Small-4's 592 B/env rows, 16 for Medium-8's 2.6 KB, 4 for Large-16's 9.3 KB
+  // (profiles/r05_obseb0_ab.txt: 8 -> 4 is 119.5 -> 115.2 us, and 133 -> 130 us for the sampler
+  // route, profiles/r05_obseb1_ab.txt 120.6 -> 114.8 us); the fragment operand alone 64 / 16 / 8
+  // (Large-16: 16 is 3 % and 4 is 20 % slower than 8, profiles/r05_obseb1_ab.txt / r05_obseb0_ab.txt)
+  const int row_bytes = 4 * g.NA * g.L;
+  int sel = row_bytes <= 1024 ? 3 : (row_bytes <= 4096 ? 2 : (obs ? 0 : 1));
+  // the fragment operand is written in whole 32-row tiles per workgroup: groups of 64 envs hold
+  // 64 * NA rows, a multiple of 32 for every agent count (e.g. Medium with 9 agents, whose f32-row
+  // grouping of 16 envs = 144 rows does not)
+  if (xfrag && (kObsEB[sel] * g.NA) % 32 != 0) sel = 3;
+  const int ebx = kObsEB[sel];
+  const int64_t qe = (int64_t)g.NA * g.L / 4;
+  if (sel == 0 && !xfrag && quads && k->observe_chunk && kObsChunk <= (ebx - 1) * qe + 1) {
+    hipLaunchKernelGGL(k->observe_chunk, dim3((unsigned)((B * qe + kObsChunk - 1) / kObsChunk)), dim3(BT), 0,
+                       (hipStream_t)stream, state, B, g.NA, tab, obs, quads, static_cast<uint4*>(xfrag));
+    return hip_err(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k->observe[sel], dim3((unsigned)((B + ebx - 1) / ebx)), dim3(BT), 0,
+                     (hipStream_t)stream, state, B, g.NA, tab, obs, quads, static_cast<uint4*>(xfrag));
+  return hip_err(hipGetLastError());
+}
+
+static int observe_impl(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void* xfrag,
+                        void* stream) {
+  Geometry g;
+  const Kernels* k;
+  const uint32_t* tab;
+  int rc = prepare(cfg, B, stream, &g, &k, &tab);
+  if (rc) return rc;
+  if (B == 0) return WH_OK;
+  if (!state || (!obs && !xfrag) || (uintptr_t)xfrag % 16 != 0) return WH_EINVAL;
+  return observe_launch(g, k, tab, B, state, obs, xfrag, stream);
+}
+
+// May the rows of a resolved step be written by its own launch (a k_sampler instance `fk`: the step
+// on half of each workgroup, every env's rows by all of it)?  Only while an env's rows are small
+// (fuse_rows) and whole float4s, and `fk` keeps its registers (fused_ok); WH_SAMPLER_UNFUSED=1 forces
+// the two launches (A/B runs).
+static bool rows_fusable(const wh_launch& l, void (*fk)(StepParams, float*), const float* obs) {
+  static const bool unfused = getenv("WH_SAMPLER_UNFUSED") != nullptr;
+  return obs && !unfused && fuse_rows(l.g) && fk && fused_ok(fk) && (l.g.NA * l.g.L) % 4 == 0 &&
+         (uintptr_t)obs % 16 == 0;
+}
+static int enqueue_fused(const wh_launch& l, void (*fk)(StepParams, float*), float* obs) {
+  hipLaunchKernelGGL(fk, grid_for(l.a.B), dim3(2 * BT), 0, l.stream, l.a, obs);
+  return hip_err(hipGetLastError());
+}
+
+// wh_vector_step and its twins: the step, then the rows of every env (stepped or not) as f32
+// (c.obs), as the policy network's fragment-order operand (c.xfrag), or not at all.  The lane-per-env
+// f32 form takes one launch when it may: the fast k_sampler instance when the step resolved to the
+// fast kernel (every env stepped in ascending order, no metrics, auto-reset: RLlib's common case),
+// else the generic one.  The operand form keeps the two launches (k_sampler writing the operand
+// from its images ran 1.8 % slower per policy step, profiles/r05_vsx_ab.txt: the operand's per-byte
+// gathers at 8 waves per CU against k_observe's full occupancy), and so does the wide step.
+static int vector_step(const StepCall& c, void* stream) {
+  wh_launch l;
+  int rc = resolve_step(c, stream, &l);
+  if (rc || c.B == 0) return rc;
+  if (c.lanes == 1 && c.obs) {
+    void (*fk)(StepParams, float*) =
+        (l.kern == l.k->step_fast[0] && l.k->sampler[0]) ? l.k->sampler[0] : l.k->vsampler[c.order ? 1 : 0];
+    if (rows_fusable(l, fk, c.obs)) return enqueue_fused(l, fk, c.obs);
+  }
+  rc = enqueue(l);
+  if (rc || (!c.obs && !c.xfrag)) return rc;
+  return observe_launch(l.g, l.k, l.a.tables, c.B, c.state, c.obs, c.xfrag, stream);
+}
+
+// One sampler step: one launch (k_sampler: the fused rollout's step, then the rows) when the fast
+// step instance applies and the rows may be fused; otherwise the step launch and k_observe.
+static int sampler_step(const StepCall& c, void* stream) {
+  wh_launch l;
+  int rc = resolve_step(c, stream, &l);
+  if (rc || c.B == 0) return rc;
+  if (l.kern == l.k->step_fast[c.policy] && rows_fusable(l, l.k->sampler[c.policy], c.obs))
+    return enqueue_fused(l, l.k->sampler[c.policy], c.obs);
+  rc = enqueue(l);
+  if (rc || !c.obs) return rc;
+  return observe_launch(l.g, l.k, l.a.tables, c.B, c.state, c.obs, nullptr, stream);
 }
 
 extern "C" {
@@ -3119,62 +3223,34 @@ extern "C" {
 int wh_step(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
             const int32_t* order, int32_t order_len, float* rewards, uint8_t* dones, const int32_t* regen,
             int32_t* n_inactive, int32_t phase, uint64_t seed, int64_t env_offset, void* stream) {
-  if (phase < WH_PHASE_ALL || phase > WH_PHASE_REGEN) return WH_EINVAL;
-  if (B > 0 && phase != WH_PHASE_REGEN && !actions) return WH_EINVAL;
-  StepParams a{};
-  a.actions = actions;
-  a.order = order;
-  a.ol = order_len;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.regen = regen;
-  a.n_inactive = n_inactive;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = phase;
-  return launch_step(cfg, B, state, POL_EXTERNAL, a, stream);
+  StepCall c;
+  const int rc = wh_abi::step_call(&c, cfg, B, state, actions, order, order_len, rewards, dones, regen, n_inactive,
+                                   phase, seed, env_offset, 1);
+  return rc ? rc : launch_step(c, stream);
 }
 
 int wh_policy(const wh_config* cfg, int64_t B, const uint32_t* state, int32_t policy, float p,
               int32_t* actions, uint64_t seed, int64_t env_offset, void* stream) {
-  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || (B > 0 && !actions)) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f)) return WH_EINVAL;
-  StepParams a{};
-  a.actions_out = actions;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 0;
-  a.phase = PH_POLICY;
-  return launch_step(cfg, B, const_cast<uint32_t*>(state), policy, a, stream);
+  StepCall c;
+  const int rc = wh_abi::policy_call(&c, cfg, B, state, policy, p, actions, seed, env_offset);
+  return rc ? rc : launch_step(c, stream);
 }
 
-static bool stats_ok(const wh_episode_stats* st) {
-  return !st || st->episode_return || (!st->return_sum && !st->episodes && !st->return_min && !st->return_max);
+int wh_rollout_wide(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
+                    float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
+                    int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes,
+                    void* stream) {
+  StepCall c;
+  const int rc = wh_abi::rollout_call(&c, cfg, B, state, steps, policy, p, rewards, dones, returns, stats, autoreset,
+                                      variable_n, seed, env_offset, lanes);
+  return rc ? rc : launch_step(c, stream);
 }
 
 int wh_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy,
                float p, float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
                int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream) {
-  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || steps < 0) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  if (stats) a.stats = *stats;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.returns = returns;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = steps;
-  a.phase = PH_ALL;
-  a.autoreset = autoreset ? 1 : 0;
-  a.variable_n = variable_n ? 1 : 0;
-  return launch_step(cfg, B, state, policy, a, stream);
+  return wh_rollout_wide(cfg, B, state, steps, policy, p, rewards, dones, returns, stats, autoreset, variable_n, seed,
+                         env_offset, 1, stream);
 }
 
 int wh_rollout_prepare(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy,
@@ -3183,24 +3259,13 @@ int wh_rollout_prepare(const wh_config* cfg, int64_t B, uint32_t* state, int32_t
                        wh_launch** out) {
   if (!out) return WH_EINVAL;
   *out = nullptr;
-  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || steps < 0) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  if (stats) a.stats = *stats;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.returns = returns;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = steps;
-  a.phase = PH_ALL;
-  a.autoreset = autoreset ? 1 : 0;
-  a.variable_n = variable_n ? 1 : 0;
+  StepCall c;
+  int rc = wh_abi::rollout_call(&c, cfg, B, state, steps, policy, p, rewards, dones, returns, stats, autoreset,
+                                variable_n, seed, env_offset, 1);
+  if (rc) return rc;
   wh_launch* l = new (std::nothrow) wh_launch;
   if (!l) return WH_EINVAL;
-  const int rc = resolve_step(cfg, B, state, policy, a, stream, l);
+  rc = resolve_step(c, stream, l);
   if (rc) {
     delete l;
     return rc;
@@ -3234,40 +3299,6 @@ int wh_launch_free(wh_launch* l) {
   return WH_OK;
 }
 
-static int observe_impl(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void* xfrag,
-                        void* stream) {
-  Geometry g;
-  const Kernels* k;
-  const uint32_t* tab;
-  int rc = prepare(cfg, B, stream, &g, &k, &tab);
-  if (rc) return rc;
-  if (B == 0) return WH_OK;
-  if (!state || (!obs && !xfrag)) return WH_EINVAL;
-  const int quads = ((g.NA * (9 * g.R + 1)) % 4 == 0) && ((uintptr_t)obs % 16 == 0);
-  // envs per workgroup (same-box A/Bs, tools/obs_bench.py and tools/sampler_probe.py): f32 rows 64
-  // for Small-4's 592 B/env rows, 16 for Medium-8's 2.6 KB, 4 for Large-16's 9.3 KB
-  // (profiles/r05_obseb0_ab.txt: 8 -> 4 is 119.5 -> 115.2 us, and 133 -> 130 us for the sampler
-  // route, profiles/r05_obseb1_ab.txt 120.6 -> 114.8 us); the fragment operand alone 64 / 16 / 8
-  // (Large-16: 16 is 3 % and 4 is 20 % slower than 8, profiles/r05_obseb1_ab.txt / r05_obseb0_ab.txt)
-  const int row_bytes = 4 * g.NA * (9 * g.R + 1);
-  int sel = row_bytes <= 1024 ? 3 : (row_bytes <= 4096 ? 2 : (obs ? 0 : 1));
-  if (xfrag && (uintptr_t)xfrag % 16 != 0) return WH_EINVAL;
-  // the fragment operand is written in whole 32-row tiles per workgroup: groups of 64 envs hold
-  // 64 * NA rows, a multiple of 32 for every agent count (e.g. Medium with 9 agents, whose f32-row
-  // grouping of 16 envs = 144 rows does not)
-  if (xfrag && (kObsEB[sel] * g.NA) % 32 != 0) sel = 3;
-  const int ebx = kObsEB[sel];
-  const int64_t qe = (int64_t)g.NA * (9 * g.R + 1) / 4;
-  if (sel == 0 && !xfrag && quads && k->observe_chunk && kObsChunk <= (ebx - 1) * qe + 1) {
-    hipLaunchKernelGGL(k->observe_chunk, dim3((unsigned)((B * qe + kObsChunk - 1) / kObsChunk)), dim3(BT), 0,
-                       (hipStream_t)stream, state, B, g.NA, tab, obs, quads, static_cast<uint4*>(xfrag));
-    return hip_err(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k->observe[sel], dim3((unsigned)((B + ebx - 1) / ebx)), dim3(BT), 0,
-                     (hipStream_t)stream, state, B, g.NA, tab, obs, quads, static_cast<uint4*>(xfrag));
-  return hip_err(hipGetLastError());
-}
-
 int wh_observe(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void* stream) {
   return observe_impl(cfg, B, state, obs, nullptr, stream);
 }
@@ -3280,259 +3311,85 @@ int wh_vector_step(const wh_config* cfg, int64_t B, uint32_t* state, const int32
                    const int32_t* order, int32_t order_len, const uint8_t* mask, float* rewards, uint8_t* dones,
                    float* obs, const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n,
                    uint64_t seed, int64_t env_offset, void* stream) {
-  if (B > 0 && !actions) return WH_EINVAL;
-  if (!stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  a.actions = actions;
-  a.order = order;   // non-NULL: the action-dict order path (k_step<..., ORDERED>), as wh_step
-  a.ol = order_len;
-  a.mask = mask;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = PH_ALL;
-  a.autoreset = autoreset ? 1 : 0;
-  a.variable_n = variable_n ? 1 : 0;
-  if (stats) a.stats = *stats;
-  wh_launch l;
-  int rc = resolve_step(cfg, B, state, POL_EXTERNAL, a, stream, &l);
-  if (rc) return rc;
-  // one launch (k_sampler's generic instance: the step on half of each workgroup, every env's rows
-  // by all of it) when its step code keeps its registers and the rows are whole float4s
-  static const bool unfused = getenv("WH_SAMPLER_UNFUSED") != nullptr;
-  Geometry g;
-  const Kernels* k = nullptr;
-  const uint32_t* tab = nullptr;
-  if (obs && !unfused && B > 0 && prepare(cfg, B, stream, &g, &k, &tab) == WH_OK && fuse_rows(g)) {
-    // the fast instance when the step resolved to it (every env stepped in ascending order, no
-    // metrics, auto-reset: RLlib's common case), else the generic one
-    void (*fk)(StepParams, float*) = (l.kern == k->step_fast[0] && k->sampler[0]) ? k->sampler[0] : k->vsampler[order ? 1 : 0];
-    if (fk && fused_ok(fk) && (g.NA * (9 * g.R + 1)) % 4 == 0 && (uintptr_t)obs % 16 == 0) {
-      hipLaunchKernelGGL(fk, grid_for(B), dim3(2 * BT), 0, l.stream, l.a, obs);
-      return hip_err(hipGetLastError());
-    }
-  }
-  rc = enqueue(l);
-  if (rc || !obs) return rc;
-  return wh_observe(cfg, B, state, obs, stream);
+  StepCall c;
+  const int rc = wh_abi::vector_step_call(&c, cfg, B, state, actions, order, order_len, mask, rewards, dones, obs,
+                                          nullptr, false, stats, autoreset, variable_n, seed, env_offset, 1);
+  return rc ? rc : vector_step(c, stream);
 }
 
 // wh_vector_step with the rows written as the policy network's fragment-order operand (the policy
-// route, scripts/rollout.py:72 -> env.step): the step launch, then wh_observe_x.  (k_sampler writing
-// the operand from its images in the step launch ran 1.8 % slower per policy step than the two
-// launches, profiles/r05_vsx_ab.txt: the operand's per-byte gathers at 8 waves per CU against
-// k_observe's full occupancy.)
+// route, scripts/rollout.py:72 -> env.step)
 int wh_vector_step_x(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
                      const int32_t* order, int32_t order_len, const uint8_t* mask, float* rewards, uint8_t* dones,
                      void* xfrag, const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n,
                      uint64_t seed, int64_t env_offset, void* stream) {
-  if (B > 0 && (!actions || !xfrag)) return WH_EINVAL;
-  if ((uintptr_t)xfrag % 16 != 0 || !stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  a.actions = actions;
-  a.order = order;
-  a.ol = order_len;
-  a.mask = mask;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = PH_ALL;
-  a.autoreset = autoreset ? 1 : 0;
-  a.variable_n = variable_n ? 1 : 0;
-  if (stats) a.stats = *stats;
-  wh_launch l;
-  int rc = resolve_step(cfg, B, state, POL_EXTERNAL, a, stream, &l);
-  if (rc) return rc;
-  if (B == 0) return WH_OK;
-  rc = enqueue(l);
-  if (rc) return rc;
-  return wh_observe_x(cfg, B, state, nullptr, xfrag, stream);
+  StepCall c;
+  const int rc = wh_abi::vector_step_call(&c, cfg, B, state, actions, order, order_len, mask, rewards, dones, nullptr,
+                                          xfrag, true, stats, autoreset, variable_n, seed, env_offset, 1);
+  return rc ? rc : vector_step(c, stream);
 }
 
 int wh_sampler_step(const wh_config* cfg, int64_t B, uint32_t* state, int32_t policy, float p,
                     float* rewards, uint8_t* dones, float* obs, const wh_episode_stats* stats,
                     int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream) {
-  if (policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  if (stats) a.stats = *stats;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = PH_ALL;
-  a.autoreset = 1;
-  a.variable_n = variable_n ? 1 : 0;
-  wh_launch l;
-  int rc = resolve_step(cfg, B, state, policy, a, stream, &l);
-  if (rc) return rc;
-  // One launch (k_sampler: the fused rollout's step on half of each workgroup, then the rows by
-  // all of it) when the fast step instance applies and the rows are whole float4s; otherwise the
-  // step launch and k_observe.  WH_SAMPLER_UNFUSED=1 forces the two launches (A/B runs).
-  static const bool unfused = getenv("WH_SAMPLER_UNFUSED") != nullptr;
-  Geometry g;
-  const Kernels* k = nullptr;
-  const uint32_t* tab = nullptr;
-  if (obs && !unfused && B > 0 && prepare(cfg, B, stream, &g, &k, &tab) == WH_OK && fuse_rows(g) && l.kern == k->step_fast[policy] &&
-      k->sampler[policy] && fused_ok(k->sampler[policy]) && (g.NA * (9 * g.R + 1)) % 4 == 0 && (uintptr_t)obs % 16 == 0) {
-    hipLaunchKernelGGL(k->sampler[policy], grid_for(B), dim3(2 * BT), 0, l.stream, l.a, obs);
-    return hip_err(hipGetLastError());
-  }
-  rc = enqueue(l);
-  if (rc || !obs) return rc;
-  return wh_observe(cfg, B, state, obs, stream);
+  StepCall c;
+  const int rc = wh_abi::sampler_step_call(&c, cfg, B, state, nullptr, false, policy, p, rewards, dones, obs, stats,
+                                           variable_n, seed, env_offset);
+  return rc ? rc : sampler_step(c, stream);
 }
 
 int wh_sampler_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
                        float* rewards, uint8_t* dones, float* obs, const wh_episode_stats* stats, int32_t variable_n,
                        uint64_t seed, int64_t env_offset, void* stream) {
-  if (policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) return WH_EINVAL;
-  if (steps < 0 || !(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  if (B > 0 && steps > 0 && !obs) return WH_EINVAL;
-  StepParams a{};
-  if (stats) a.stats = *stats;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = steps;
-  a.phase = PH_ALL;
-  a.autoreset = 1;
-  a.variable_n = variable_n ? 1 : 0;
+  StepCall c;
+  int rc = wh_abi::sampler_rollout_call(&c, cfg, B, state, steps, policy, p, rewards, dones, obs, stats, variable_n,
+                                        seed, env_offset);
+  if (rc) return rc;
   wh_launch l;
-  int rc = resolve_step(cfg, B, state, policy, a, stream, &l);
+  rc = resolve_step(c, stream, &l);
   if (rc || B == 0 || steps == 0) return rc;
-  Geometry g;
-  const Kernels* k = nullptr;
-  const uint32_t* tab = nullptr;
-  if ((rc = prepare(cfg, B, stream, &g, &k, &tab)) != WH_OK) return rc;
-  static const bool unfused = getenv("WH_SAMPLER_UNFUSED") != nullptr;
-  void (*fk)(StepParams, float*) = steps == 1 ? k->sampler[policy] : k->sampler_multi[policy];
-  if (!unfused && fuse_rows(g) && l.kern == k->step_fast[policy] && fk && fused_ok(fk) && (g.NA * (9 * g.R + 1)) % 4 == 0 &&
-      (uintptr_t)obs % 16 == 0) {
-    hipLaunchKernelGGL(fk, grid_for(B), dim3(2 * BT), 0, l.stream, l.a, obs);
-    return hip_err(hipGetLastError());
-  }
+  void (*fk)(StepParams, float*) = steps == 1 ? l.k->sampler[policy] : l.k->sampler_multi[policy];
+  if (l.kern == l.k->step_fast[policy] && rows_fusable(l, fk, obs)) return enqueue_fused(l, fk, obs);
   // otherwise: the same steps one launch (pair) at a time
-  const int64_t rows = B * (int64_t)g.NA * (9 * g.R + 1);
-  for (int32_t t = 0; t < steps && rc == WH_OK; ++t)
-    rc = wh_sampler_step(cfg, B, state, policy, p, rewards ? rewards + (int64_t)t * B * g.NA : nullptr,
-                         dones ? dones + (int64_t)t * B : nullptr, obs + (int64_t)t * rows, stats, variable_n, seed,
-                         env_offset, stream);
+  c.steps = 1;
+  for (int32_t t = 0; t < steps && rc == WH_OK; ++t) {
+    rc = sampler_step(c, stream);
+    if (c.rewards) c.rewards += B * c.g.NA;
+    if (c.dones) c.dones += B;
+    c.obs += B * c.g.NA * c.g.L;
+  }
   return rc;
 }
 
 int wh_sampler_step_to(const wh_config* cfg, int64_t B, const uint32_t* state_in, uint32_t* state_out,
                        int32_t policy, float p, float* rewards, uint8_t* dones, const wh_episode_stats* stats,
                        int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream) {
-  if (policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  if (B > 0 && !state_out) return WH_EINVAL;
-  StepParams a{};
-  if (stats) a.stats = *stats;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = PH_ALL;
-  a.autoreset = 1;
-  a.variable_n = variable_n ? 1 : 0;
-  a.state_out = state_out;   // every env is live (no mask): each lane stores its whole state
-  return launch_step(cfg, B, const_cast<uint32_t*>(state_in), policy, a, stream);
+  StepCall c;
+  const int rc = wh_abi::sampler_step_call(&c, cfg, B, state_in, state_out, true, policy, p, rewards, dones, nullptr,
+                                           stats, variable_n, seed, env_offset);
+  return rc ? rc : launch_step(c, stream);
 }
-
 
 // ---- the 16-lanes-per-env execution form (csrc/step_wide.h).  lanes == WH_WIDE_LANES runs
 // k_step_wide; lanes == 1 is the lane-per-env entry point itself (ascending order, whole step).
 int wh_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions, float* rewards,
                  uint8_t* dones, const int32_t* regen, int32_t* n_inactive, uint64_t seed, int64_t env_offset,
                  int32_t lanes, void* stream) {
-  if (lanes == 1)
-    return wh_step(cfg, B, state, actions, nullptr, 0, rewards, dones, regen, n_inactive, WH_PHASE_ALL, seed,
-                   env_offset, stream);
-  if (lanes != WH_WIDE_LANES) return WH_EINVAL;
-  if (B > 0 && !actions) return WH_EINVAL;
-  StepParams a{};
-  a.actions = actions;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.regen = regen;
-  a.n_inactive = n_inactive;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = PH_ALL;
-  return launch_step(cfg, B, state, POL_EXTERNAL, a, stream, lanes);
+  StepCall c;
+  const int rc = wh_abi::step_call(&c, cfg, B, state, actions, nullptr, 0, rewards, dones, regen, n_inactive,
+                                   WH_PHASE_ALL, seed, env_offset, lanes);
+  return rc ? rc : launch_step(c, stream);
 }
 
-int wh_rollout_wide(const wh_config* cfg, int64_t B, uint32_t* state, int32_t steps, int32_t policy, float p,
-                    float* rewards, uint8_t* dones, float* returns, const wh_episode_stats* stats,
-                    int32_t autoreset, int32_t variable_n, uint64_t seed, int64_t env_offset, int32_t lanes,
-                    void* stream) {
-  if (lanes == 1)
-    return wh_rollout(cfg, B, state, steps, policy, p, rewards, dones, returns, stats, autoreset, variable_n, seed,
-                      env_offset, stream);
-  if (lanes != WH_WIDE_LANES) return WH_EINVAL;
-  if ((policy != WH_POLICY_GREEDY && policy != WH_POLICY_RANDOM) || steps < 0) return WH_EINVAL;
-  if (!(p >= 0.0f && p <= 1.0f) || !stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  if (stats) a.stats = *stats;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.returns = returns;
-  a.p = p;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = steps;
-  a.phase = PH_ALL;
-  a.autoreset = autoreset ? 1 : 0;
-  a.variable_n = variable_n ? 1 : 0;
-  return launch_step(cfg, B, state, policy, a, stream, lanes);
-}
-
-// the wide step launch, then k_observe (wh_observe): two launches
+// the wide step launch, then k_observe: two launches
 int wh_vector_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* actions,
                         const uint8_t* mask, float* rewards, uint8_t* dones, float* obs,
                         const wh_episode_stats* stats, int32_t autoreset, int32_t variable_n, uint64_t seed,
                         int64_t env_offset, int32_t lanes, void* stream) {
-  if (lanes == 1)
-    return wh_vector_step(cfg, B, state, actions, nullptr, 0, mask, rewards, dones, obs, stats, autoreset,
-                          variable_n, seed, env_offset, stream);
-  if (lanes != WH_WIDE_LANES) return WH_EINVAL;
-  if (B > 0 && !actions) return WH_EINVAL;
-  if (!stats_ok(stats)) return WH_EINVAL;
-  StepParams a{};
-  a.actions = actions;
-  a.mask = mask;
-  a.rewards = rewards;
-  a.dones = dones;
-  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
-  a.k1 = (uint32_t)(seed >> 32);
-  a.env_offset = env_offset;
-  a.steps = 1;
-  a.phase = PH_ALL;
-  a.autoreset = autoreset ? 1 : 0;
-  a.variable_n = variable_n ? 1 : 0;
-  if (stats) a.stats = *stats;
-  const int rc = launch_step(cfg, B, state, POL_EXTERNAL, a, stream, lanes);
-  if (rc || !obs) return rc;
-  return wh_observe(cfg, B, state, obs, stream);
+  StepCall c;
+  const int rc = wh_abi::vector_step_call(&c, cfg, B, state, actions, nullptr, 0, mask, rewards, dones, obs, nullptr,
+                                          false, stats, autoreset, variable_n, seed, env_offset, lanes);
+  return rc ? rc : vector_step(c, stream);
 }
 
 }  // extern "C"

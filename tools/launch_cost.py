@@ -5,6 +5,7 @@ latency, kernel prologue/epilogue, completion/sync latency.  Medium-8, B = 65,53
 Prints medians (us) over repetitions:
   sync_idle      torch.cuda.synchronize() on an idle device
   tiny_op        a one-element torch op + sync (launch + completion latency of a trivial kernel)
+  vector_step_call  one wh_vector_step call with observation rows (host time of the C call, no sync)
   call_K         the bound wh_rollout call alone (host time, no sync)
   wall_K         call + sync (what bench.py's window sees for one launch of K steps)
   event_K        HIP-event span around the launch on its stream
@@ -54,6 +55,16 @@ def main():
         torch.cuda.synchronize()
         r.append(e0.elapsed_time(e1) * 1e-3)
     print(f"tiny_op_event {med(r):8.1f}")
+    acts = torch.full((B, NA), 4, dtype=torch.int32, device=dev)
+    obs = torch.empty((B, NA, env.obs_len), dtype=torch.float32, device=dev)
+    args = (env._cfgp, B, env.state.data_ptr(), acts.data_ptr(), None, 0, None, env.rewards.data_ptr(),
+            env.dones.data_ptr(), obs.data_ptr(), None, 1, 0, env.seed, env.env_offset, env.stream)
+    r = []
+    for _ in range(53):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter(); rc = env._lib.wh_vector_step(*args); r.append(time.perf_counter() - t0)
+        assert rc == 0, rc
+    print(f"vector_step_call {med(r[3:]):8.1f}")
     Ks = (20,) if "--quick" in sys.argv else (0, 1, 2, 5, 20, 200)
     for K in Ks:
         rew = torch.zeros((K, B, NA), device=dev)
