@@ -34,7 +34,8 @@
  * INJECTED (explicit arrays below: bit-exact parity with the reference given its draws) or taken
  * from the PHILOX contract: Philox4x32-10 keyed by `seed`, counter (env_offset + e, episode, t,
  * purpose << 24 | block); purposes RESET=1, REGEN=2, POLICY=3, RANDOM=4 (word layout in
- * DESIGN.md §RNG and oracle/philox.py).  Philox trajectories depend only on the global env id,
+ * DESIGN.md §RNG and oracle/philox.py; 5 = the policy network's sampling noise, 6 = replay index
+ * draws, with the counters their entry points state).  Philox trajectories depend only on the global env id,
  * so any sharding of env ids over GPUs reproduces them exactly.
  */
 #ifndef WAREHOUSE_AMD_H
@@ -313,6 +314,63 @@ int wh_mlp_forward(const wh_mlp_desc* d, const void* packed, int64_t rows, const
 int wh_mlp_forward_x(const wh_mlp_desc* d, const void* packed, int64_t rows, const void* xfrag,
                      float* logits, int32_t* actions, int32_t explore, uint64_t seed, uint32_t step,
                      void* stream);
+
+/* REPLAY RING: off-policy transitions kept as packed states instead of observation rows (every row
+ * is a function of the packed state: 265 bytes per Medium-8 transition against 5,289 as f32 rows).
+ * A ring holds `capacity` slots; a slot is one time step of all B envs.  The buffers are device
+ * memory (host memory for the host engine) owned by the caller, sized exactly as stated; the layout
+ * is the same for both engines, so a ring moves between them with a plain copy.  Records are
+ * env-major -- states[((slot * 2 + side) * B + e) * words_per_env + w] is word w of env e -- so a
+ * sampled transition reads one contiguous record per side. */
+typedef struct wh_replay_ring {
+  uint32_t* states;   /* [capacity, 2, B, words_per_env]  env-major records; side 0 = the state the
+                         actions were chosen from, side 1 = the state after the step and BEFORE any reset */
+  uint8_t*  actions;  /* [capacity, B, NA]  0..8 */
+  float*    rewards;  /* [capacity, B, NA] */
+  uint8_t*  dones;    /* [capacity, B] */
+  int64_t   capacity; /* slots (time steps), >= 1 */
+} wh_replay_ring;
+
+/* Record one half of slot `slot` (0 <= slot < capacity) from the live [words, B] state, one launch:
+ *   stage 0  side 0 of the slot <- state; ring actions <- actions (int32 [B,NA]; values outside 0..8
+ *            are kept as 4 = stay, what the step does with them)
+ *   stage 1  side 1 of the slot <- state; ring rewards / dones <- rewards (f32 [B,NA]) / dones (u8 [B])
+ * The sequence of one recorded step is put(0), a step WITHOUT auto-reset, put(1), then the reset of
+ * the done envs: side 1 of a done env is its terminal state (the reference trains with
+ * no_done_at_end, so the bootstrap reads the terminal observation), and the next slot's side 0 the
+ * fresh state.  The pointers a stage does not read may be NULL. */
+int wh_replay_put(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t slot, int32_t stage,
+                  const uint32_t* state, const int32_t* actions, const float* rewards, const uint8_t* dones,
+                  void* stream);
+
+/* Outputs of wh_replay_gather for M samples; any may be NULL, not all.  obs / next_obs are the rows
+ * of wh_observe on side 0 / side 1, xfrag / next_xfrag wh_observe_x's operand for a batch of M envs
+ * (device only, 16-byte aligned), state / next_state plane-major packed states [words, M] (usable by
+ * every entry that takes a state of M envs). */
+typedef struct wh_replay_batch {
+  float*    obs;         /* [M, NA, 9R+1] */
+  float*    next_obs;    /* [M, NA, 9R+1] */
+  void*     xfrag;       /* [ceil(M*NA/32), KQ, 64, 16] bytes */
+  void*     next_xfrag;
+  uint32_t* state;       /* [words, M] */
+  uint32_t* next_state;  /* [words, M] */
+  int32_t*  actions;     /* [M, NA] */
+  float*    rewards;     /* [M, NA] */
+  uint8_t*  dones;       /* [M]  as recorded */
+  int32_t*  n;           /* [M]  live agents of side 0 (rows >= n are zero); -1 = invalid index */
+  int64_t*  idx_out;     /* [M]  the indices used */
+} wh_replay_batch;
+
+/* Gather M transitions of the first `filled` slots (1 <= filled <= capacity) into learner inputs, one
+ * launch.  idx [M] int64, each slot * B + env, duplicates and any order allowed; idx = NULL draws
+ * them from the philox contract, purpose 6: counter (m, draw & 0xFFFFFFFF, draw >> 32, 6 << 24) keyed
+ * by seed, slot = uniform_int(filled, word 0), env = uniform_int(B, word 1).  An index outside
+ * [0, filled * B) reads nothing: n[m] = -1 and every other output of sample m is zero (fragment
+ * rows keep their two 1.0 columns).  obs / next_obs are written as float4 when NA * (9R+1) is a
+ * multiple of 4 and must then be 16-byte aligned.  M = 0 or B = 0 launch nothing.  The host engine
+ * returns WH_ENOTSUP when a fragment output is requested. */
+int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t filled, int64_t M,
+                     const int64_t* idx, uint64_t seed, uint64_t draw, const wh_replay_batch* batch, void* stream);
 
 /* Library build identification (e.g. "warehouse_amd gfx950 <date>"). */
 const char* wh_version(void);

@@ -213,4 +213,46 @@ inline int sampler_rollout_call(StepCall* c, const wh_config* cfg, int64_t B, ui
   return finish(c, cfg);
 }
 
+// ----------------------------------------------------------------------------- replay ring
+// The same order as the step family: the entry point's own options and required pointers, the
+// config, the state pointer (put) or the alignment that depends on the config (gather), B < 0.
+inline bool ring_ok(const wh_replay_ring* ring) { return ring && ring->capacity >= 1; }
+
+// wh_replay_put
+inline int replay_put_call(Shape* g, const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t slot,
+                           int32_t stage, const uint32_t* state, const int32_t* actions, const float* rewards,
+                           const uint8_t* dones) {
+  if (!ring_ok(ring) || slot < 0 || slot >= ring->capacity || (stage != 0 && stage != 1)) return WH_EINVAL;
+  if (B > 0) {
+    if (!ring->states) return WH_EINVAL;
+    if (stage == 0 && (!ring->actions || !actions)) return WH_EINVAL;
+    if (stage == 1 && (!ring->rewards || !ring->dones || !rewards || !dones)) return WH_EINVAL;
+  }
+  const int rc = check_config(cfg, g);
+  if (rc) return rc;
+  return ((B > 0 && !state) || B < 0) ? WH_EINVAL : WH_OK;
+}
+
+inline bool batch_has_frags(const wh_replay_batch* b) { return b->xfrag || b->next_xfrag; }
+
+// wh_replay_gather
+inline int replay_gather_call(Shape* g, const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t filled,
+                              int64_t M, const wh_replay_batch* b) {
+  if (!ring_ok(ring) || filled < 1 || filled > ring->capacity || M < 0 || !b) return WH_EINVAL;
+  if (!b->obs && !b->next_obs && !b->xfrag && !b->next_xfrag && !b->state && !b->next_state && !b->actions &&
+      !b->rewards && !b->dones && !b->n && !b->idx_out)
+    return WH_EINVAL;
+  if (B > 0 && M > 0) {
+    if (!ring->states) return WH_EINVAL;
+    if ((b->actions && !ring->actions) || (b->rewards && !ring->rewards) || (b->dones && !ring->dones))
+      return WH_EINVAL;
+  }
+  if ((uintptr_t)b->xfrag % 16 != 0 || (uintptr_t)b->next_xfrag % 16 != 0) return WH_EINVAL;
+  const int rc = check_config(cfg, g);
+  if (rc) return rc;
+  if ((g->NA * g->L) % 4 == 0 && ((uintptr_t)b->obs % 16 != 0 || (uintptr_t)b->next_obs % 16 != 0))
+    return WH_EINVAL;   // rows written as float4
+  return B < 0 ? WH_EINVAL : WH_OK;
+}
+
 }  // namespace wh_abi

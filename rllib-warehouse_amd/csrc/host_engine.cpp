@@ -772,6 +772,80 @@ int wh_sampler_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t
   return WH_OK;
 }
 
+// ---- replay ring (include/warehouse_amd.h, REPLAY RING): the device's layout, index draw and
+// invalid-index rule; the rows come from observe_env
+int wh_replay_put(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t slot, int32_t stage,
+                  const uint32_t* state, const int32_t* actions, const float* rewards, const uint8_t* dones, void*) {
+  Geo g;
+  int rc = wh_abi::replay_put_call(&g, cfg, B, ring, slot, stage, state, actions, rewards, dones);
+  if (rc || (rc = make_geo(wh_abi::Shape(g), &g))) return rc;
+  if (B == 0) return WH_OK;
+  const int words = g.words, na = g.NA;
+  uint32_t* rec = ring->states + (2 * slot + stage) * B * words;
+#pragma omp parallel for schedule(static) if (B >= 1024)
+  for (int64_t e = 0; e < B; ++e) {
+    for (int w = 0; w < words; ++w) rec[e * words + w] = state[(int64_t)w * B + e];
+    if (stage == 0) {
+      for (int i = 0; i < na; ++i) {
+        const uint32_t a = (uint32_t)actions[e * na + i];
+        ring->actions[(slot * B + e) * na + i] = (uint8_t)(a > 8u ? 4u : a);
+      }
+    } else {
+      for (int i = 0; i < na; ++i) ring->rewards[(slot * B + e) * na + i] = rewards[e * na + i];
+      ring->dones[slot * B + e] = dones[e];
+    }
+  }
+  return WH_OK;
+}
+
+int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t filled, int64_t M,
+                     const int64_t* idx, uint64_t seed, uint64_t draw, const wh_replay_batch* b, void*) {
+  Geo g;
+  int rc = wh_abi::replay_gather_call(&g, cfg, B, ring, filled, M, b);
+  if (rc || (rc = make_geo(wh_abi::Shape(g), &g))) return rc;
+  if (wh_abi::batch_has_frags(b)) return WH_ENOTSUP;   // the fragment operand is a device format
+  if (B == 0 || M == 0) return WH_OK;
+  const int words = g.words, na = g.NA;
+  const int64_t row = (int64_t)na * g.L;
+  const uint32_t k0 = keys_lo(seed), k1 = keys_hi(seed);
+#pragma omp parallel for schedule(static) if (M >= 1024)
+  for (int64_t m = 0; m < M; ++m) {
+    int64_t ix;
+    if (idx) {
+      ix = idx[m];
+      if (ix < 0 || ix >= filled * B) ix = -1;
+    } else {
+      const U4 r = philox10((uint32_t)m, (uint32_t)(draw & 0xFFFFFFFFu), (uint32_t)(draw >> 32), 6u << 24, k0, k1);
+      ix = (int64_t)(((uint64_t)r.v[0] * (uint64_t)filled) >> 32) * B + (int64_t)(((uint64_t)r.v[1] * (uint64_t)B) >> 32);
+    }
+    const int64_t slot = ix < 0 ? 0 : ix / B;
+    uint32_t side_n = 0;
+    for (int side = 0; side < 2; ++side) {
+      float* rows = side ? b->next_obs : b->obs;
+      uint32_t* planes = side ? b->next_state : b->state;
+      // an invalid index reads nothing: an all-zero record (n = 0, zero rows)
+      std::vector<uint32_t> rec((size_t)words, 0u);
+      if (ix >= 0) memcpy(rec.data(), ring->states + (ix + (slot + side) * B) * words, sizeof(uint32_t) * words);
+      if (planes)
+        for (int w = 0; w < words; ++w) planes[(int64_t)w * M + m] = rec[w];
+      if (rows || side == 0) {
+        Env s;
+        load(g, rec.data(), 1, 0, s);   // (a record is a one-env word-plane state)
+        if (side == 0) side_n = s.n;
+        if (rows) observe_env(g, s, rows + m * row);
+      }
+    }
+    for (int i = 0; i < na; ++i) {
+      if (b->actions) b->actions[m * na + i] = ix < 0 ? 0 : (int32_t)ring->actions[ix * na + i];
+      if (b->rewards) b->rewards[m * na + i] = ix < 0 ? 0.0f : ring->rewards[ix * na + i];
+    }
+    if (b->dones) b->dones[m] = ix < 0 ? 0 : ring->dones[ix];
+    if (b->n) b->n[m] = ix < 0 ? -1 : (int32_t)side_n;
+    if (b->idx_out) b->idx_out[m] = ix < 0 ? 0 : ix;
+  }
+  return WH_OK;
+}
+
 // ---- what the CPU has no use for: the policy network and its fragment operand (device formats),
 // the two-stream sampler step, prepared launches, assert-mode counters, and the 16-lanes-per-env
 // form (csrc/step_wide.h: the host engine has no lanes)

@@ -2211,6 +2211,149 @@ struct ObsLds {
   uint32_t dst[C::DP];           // delivery cell, x << 8 | y << 24 | 0x00FF00FF
 };
 
+// The image build, shared by k_observe and k_replay_gather (replay.h).  It is written against a WORD
+// SOURCE: a callable w -> word w of this lane's env.  k_observe reads the live state's word planes
+// (PlaneWords: state[w * B + e]); the replay gather reads a record it has staged in LDS.  The build is
+// split where k_observe's barriers fall: issue the tables and the env's words (every global load
+// before its first use), commit the tables and write the agent rows and the pickup words, then (after
+// a barrier) the popcount-ranked requests.
+struct PlaneWords {
+  const uint32_t* st;
+  int64_t B, e;
+  __device__ __forceinline__ uint32_t operator()(int w) const { return st[w * B + e]; }
+};
+
+template <class C>
+struct ObsTabRegs {   // the per-workgroup tables in flight: gather table, pickup cells, delivery cells
+  static constexpr int SRCW = ObsSrc<C::R, C::NAM>::W;
+  static constexpr int NSRC = (2 * SRCW + BT - 1) / BT, NRP = (C::P + BT - 1) / BT, NDP = (C::DP + BT - 1) / BT;
+  uint32_t sv[NSRC], rv[NRP], dv[NDP];
+};
+template <class C>
+__device__ __forceinline__ void obs_tables_issue(ObsTabRegs<C>& t, const uint32_t* tables, int tid) {
+  using T = ObsTabRegs<C>;
+  const uint32_t* srcg = &kObsSrc<C::R, C::NAM>.w[0][0];
+#pragma unroll
+  for (int i = 0; i < T::NSRC; ++i) t.sv[i] = tid + i * BT < 2 * T::SRCW ? srcg[tid + i * BT] : 0u;
+#pragma unroll
+  for (int i = 0; i < T::NRP; ++i) t.rv[i] = tid + i * BT < C::P ? tables[C::T.rp / 4 + 2 * (tid + i * BT)] : 0u;
+#pragma unroll
+  for (int i = 0; i < T::NDP; ++i) t.dv[i] = tid + i * BT < C::DP ? tables[C::T.dst / 4 + tid + i * BT] : 0u;
+}
+template <class C, int OBS_EB>
+__device__ __forceinline__ void obs_tables_commit(ObsLds<C, OBS_EB>& O, const ObsTabRegs<C>& t, int tid) {
+  using T = ObsTabRegs<C>;
+#pragma unroll
+  for (int i = 0; i < T::NSRC; ++i)
+    if (tid + i * BT < 2 * T::SRCW) (&O.src[0][0])[tid + i * BT] = t.sv[i];
+#pragma unroll
+  for (int i = 0; i < T::NRP; ++i)
+    if (tid + i * BT < C::P) O.rp[tid + i * BT] = t.rv[i];
+#pragma unroll
+  for (int i = 0; i < T::NDP; ++i)
+    if (tid + i * BT < C::DP) O.dst[tid + i * BT] = t.dv[i];
+}
+
+template <class C, int OBS_EB>
+struct ObsEnvWords {   // this lane's share of its env's words: OBS_PARTS lanes per env
+  static constexpr int OBS_PARTS = BT / OBS_EB;
+  static constexpr int NAR = (C::R + OBS_PARTS - 1) / OBS_PARTS, NPW = (C::PW + OBS_PARTS - 1) / OBS_PARTS;
+  uint32_t av[NAR], pv[NPW], hdr;
+};
+// An agent row past n is loaded and replaced by IDLE in the image (rows r < na exist in the state).
+template <class C, int OBS_EB, class WORDS>
+__device__ __forceinline__ void obs_words_issue(ObsEnvWords<C, OBS_EB>& r, const WORDS& word, int part, int na) {
+  using E = ObsEnvWords<C, OBS_EB>;
+  r.hdr = word(0);
+#pragma unroll
+  for (int i = 0; i < E::NAR; ++i) {
+    const int a = part + i * E::OBS_PARTS;
+    r.av[i] = (a < C::R && a < na) ? word(2 + a) : IDLE;
+  }
+#pragma unroll
+  for (int i = 0; i < E::NPW; ++i) {
+    const int w = part + i * E::OBS_PARTS;
+    r.pv[i] = w < C::PW ? word(2 + na + w) : 0u;
+  }
+}
+// agent rows, n, lim and the pickup words of env slot `el` (a barrier follows)
+template <class C, int OBS_EB>
+__device__ __forceinline__ void obs_image_agents(ObsLds<C, OBS_EB>& O, const ObsEnvWords<C, OBS_EB>& r, int el,
+                                                 int part, int na) {
+  using E = ObsEnvWords<C, OBS_EB>;
+  constexpr int R = C::R, D = C::D, L = C::L;
+  constexpr int A0 = 1, G0 = 1 + R, P0 = 1 + 3 * R;
+  const uint8_t nul = (uint8_t)(D / 2);
+  uint32_t n = (r.hdr >> 16) & 0xFFu;
+  n = n < (uint32_t)na ? n : (uint32_t)na;
+  const bool fresh = (r.hdr >> 24) & 1u;
+  uint8_t* im = O.img[el];
+  if (part == 0) {
+    im[0] = (uint8_t)n;
+    O.lim[el] = n * L | (fresh ? 0x80000000u : 0u);
+  }
+#pragma unroll
+  for (int i = 0; i < E::NAR; ++i) {                       // agent rows
+    const int ar = part + i * E::OBS_PARTS;
+    if (ar < R) {
+      const bool live = ar < (int)n;
+      const uint32_t a = live ? r.av[i] : IDLE;
+      const bool carry = (a & 0xFF00u) != 0xFF00u;
+      im[A0 + ar] = (uint8_t)((live && !fresh && !carry) ? 1 : 0);
+      const bool show = live && !fresh && carry;
+      im[G0 + 2 * ar] = show ? (uint8_t)((a >> 8) & 0xFFu) : nul;
+      im[G0 + 2 * ar + 1] = show ? (uint8_t)(a >> 24) : nul;
+      im[P0 + 2 * ar] = live ? (uint8_t)(a & 0xFFu) : nul;
+      im[P0 + 2 * ar + 1] = live ? (uint8_t)((a >> 16) & 0xFFu) : nul;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < E::NPW; ++i) {
+    const int w = part + i * E::OBS_PARTS;
+    if (w < C::PW) O.ptw[el][w] = r.pv[i];
+  }
+}
+// requests of env slot `el`: ascending pickup index, ranked by the popcount of the words before
+template <class C, int OBS_EB>
+__device__ __forceinline__ void obs_image_requests(ObsLds<C, OBS_EB>& O, int el, int part) {
+  constexpr int R = C::R, Q0 = 1 + 5 * R, OBS_PARTS = BT / OBS_EB;
+  uint8_t* im = O.img[el];
+  for (int w = part; w < C::PW; w += OBS_PARTS) {
+    uint32_t r = 0;
+    for (int v = 0; v < w; ++v) r += __popc(nz_hi(O.ptw[el][v]));
+    const uint32_t pt = O.ptw[el][w];
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t tg = (pt >> (8 * b)) & 0xFFu;
+      if (tg && r < (uint32_t)R) {
+        const uint32_t pxy = O.rp[4 * w + b];
+        const uint32_t dxy = O.dst[(tg - 1u) % C::DP];   // x << 8 | y << 24 (| 0x00FF00FF)
+        im[Q0 + 4 * r] = (uint8_t)(pxy & 0xFFu);
+        im[Q0 + 4 * r + 1] = (uint8_t)(pxy >> 16);
+        im[Q0 + 4 * r + 2] = (uint8_t)(dxy >> 8);
+        im[Q0 + 4 * r + 3] = (uint8_t)(dxy >> 24);
+        ++r;
+      }
+    }
+    if (w == C::PW - 1)      // fewer than R active slots never occurs after reset/step; keep rows defined
+      for (; r < (uint32_t)R; ++r)
+        im[Q0 + 4 * r] = im[Q0 + 4 * r + 1] = im[Q0 + 4 * r + 2] = im[Q0 + 4 * r + 3] = 0;
+  }
+}
+// the rows of a group whose env rows are not whole float4s (or not 16-byte aligned): one float per lane
+template <class C, int OBS_EB>
+__device__ __forceinline__ void stream_rows_scalar(const ObsLds<C, OBS_EB>& O, float* out, uint32_t nenv,
+                                                   uint32_t per_env, int tid) {
+  const uint32_t total = nenv * per_env;
+  const uint32_t magic = 0xFFFFFFFFu / per_env + 1u;
+  for (uint32_t o = tid; o < total; o += BT) {
+    const uint32_t el1 = __umulhi(o, magic);
+    const uint32_t k = o - el1 * per_env;
+    const uint32_t lim = O.lim[el1];
+    const uint8_t* sb = reinterpret_cast<const uint8_t*>(O.src[lim >> 31]);
+    out[o] = k < (lim & 0x7FFFFFFFu) ? (float)O.img[el1][sb[k]] : 0.0f;
+  }
+}
+
 // xfrag (optional): the same rows as the policy network's layer-0 B operand (policy_mlp.hip),
 // bf16, in MFMA fragment order: 16-byte chunk ((tile * KQ + q) * 64 + lane) of agent-row tile
 // `tile` (32 rows) holds features 16q + 8h + j (j < 8) of row tile*32 + (lane & 31), h = lane >> 5;
@@ -2228,8 +2371,7 @@ __global__ __launch_bounds__(BT) void k_observe(const uint32_t* __restrict__ sta
                                                 uint4* __restrict__ xfrag) {
   __shared__ ObsLds<C, OBS_EB> O;
   constexpr int OBS_PARTS = BT / OBS_EB;
-  constexpr int R = C::R, D = C::D, L = C::L, SRCW = ObsLds<C, OBS_EB>::SRCW;
-  constexpr int A0 = 1, G0 = 1 + R, P0 = 1 + 3 * R, Q0 = 1 + 5 * R;
+  constexpr int L = C::L;
   const int tid = threadIdx.x;
   int64_t e0;
   uint32_t nenv, qlo = 0, qhi = ~0u;
@@ -2250,96 +2392,16 @@ __global__ __launch_bounds__(BT) void k_observe(const uint32_t* __restrict__ sta
   // Every global load of the prologue is issued before its first use: as strided loops, each
   // iteration compiled to a load -> vmcnt(0) -> LDS write round trip, and the agent rows waited on
   // the header (their guard was r < n) -- about eight serial memory latencies per workgroup for
-  // Large-16 (five for its 4.6 KB gather table alone), now one.  An agent row past n is loaded and
-  // replaced by IDLE below (rows r < na exist in the state).
-  constexpr int NSRC = (2 * SRCW + BT - 1) / BT, NRP = (C::P + BT - 1) / BT, NDP = (C::DP + BT - 1) / BT;
-  constexpr int NAR = (R + OBS_PARTS - 1) / OBS_PARTS, NPW = (C::PW + OBS_PARTS - 1) / OBS_PARTS;
-  const uint32_t* srcg = &kObsSrc<C::R, C::NAM>.w[0][0];
-  uint32_t sv[NSRC], rv[NRP], dv[NDP], av[NAR], pv[NPW], hdr = 0;
-#pragma unroll
-  for (int i = 0; i < NSRC; ++i) sv[i] = tid + i * BT < 2 * SRCW ? srcg[tid + i * BT] : 0u;
-#pragma unroll
-  for (int i = 0; i < NRP; ++i) rv[i] = tid + i * BT < C::P ? tables[C::T.rp / 4 + 2 * (tid + i * BT)] : 0u;
-#pragma unroll
-  for (int i = 0; i < NDP; ++i) dv[i] = tid + i * BT < C::DP ? tables[C::T.dst / 4 + tid + i * BT] : 0u;
-  if (mine) {
-    hdr = state[e];
-#pragma unroll
-    for (int i = 0; i < NAR; ++i) {
-      const int r = part + i * OBS_PARTS;
-      av[i] = (r < R && r < na) ? state[(2 + r) * B + e] : IDLE;
-    }
-#pragma unroll
-    for (int i = 0; i < NPW; ++i) {
-      const int w = part + i * OBS_PARTS;
-      pv[i] = w < C::PW ? state[(2 + na + w) * B + e] : 0u;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NSRC; ++i)
-    if (tid + i * BT < 2 * SRCW) (&O.src[0][0])[tid + i * BT] = sv[i];
-#pragma unroll
-  for (int i = 0; i < NRP; ++i)
-    if (tid + i * BT < C::P) O.rp[tid + i * BT] = rv[i];
-#pragma unroll
-  for (int i = 0; i < NDP; ++i)
-    if (tid + i * BT < C::DP) O.dst[tid + i * BT] = dv[i];
-
-  const uint8_t nul = (uint8_t)(D / 2);
-  if (mine) {
-    uint32_t n = (hdr >> 16) & 0xFFu;
-    n = n < (uint32_t)na ? n : (uint32_t)na;
-    const bool fresh = (hdr >> 24) & 1u;
-    uint8_t* im = O.img[el];
-    if (part == 0) {
-      im[0] = (uint8_t)n;
-      O.lim[el] = n * L | (fresh ? 0x80000000u : 0u);
-    }
-#pragma unroll
-    for (int i = 0; i < NAR; ++i) {                       // agent rows
-      const int r = part + i * OBS_PARTS;
-      if (r < R) {
-        const bool live = r < (int)n;
-        const uint32_t a = live ? av[i] : IDLE;
-        const bool carry = (a & 0xFF00u) != 0xFF00u;
-        im[A0 + r] = (uint8_t)((live && !fresh && !carry) ? 1 : 0);
-        const bool show = live && !fresh && carry;
-        im[G0 + 2 * r] = show ? (uint8_t)((a >> 8) & 0xFFu) : nul;
-        im[G0 + 2 * r + 1] = show ? (uint8_t)(a >> 24) : nul;
-        im[P0 + 2 * r] = live ? (uint8_t)(a & 0xFFu) : nul;
-        im[P0 + 2 * r + 1] = live ? (uint8_t)((a >> 16) & 0xFFu) : nul;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NPW; ++i) {
-      const int w = part + i * OBS_PARTS;
-      if (w < C::PW) O.ptw[el][w] = pv[i];
-    }
-  }
+  // Large-16 (five for its 4.6 KB gather table alone), now one.
+  ObsTabRegs<C> tr;
+  ObsEnvWords<C, OBS_EB> ew;
+  ew.hdr = 0;
+  obs_tables_issue<C>(tr, tables, tid);
+  if (mine) obs_words_issue<C, OBS_EB>(ew, PlaneWords{state, B, e}, part, na);
+  obs_tables_commit<C, OBS_EB>(O, tr, tid);
+  if (mine) obs_image_agents<C, OBS_EB>(O, ew, el, part, na);
   __syncthreads();
-  if (mine) {                                             // requests: ascending pickup index
-    uint8_t* im = O.img[el];
-    for (int w = part; w < C::PW; w += OBS_PARTS) {
-      uint32_t r = 0;
-      for (int v = 0; v < w; ++v) r += __popc(nz_hi(O.ptw[el][v]));
-      const uint32_t pt = O.ptw[el][w];
-      for (int b = 0; b < 4; ++b) {
-        const uint32_t tg = (pt >> (8 * b)) & 0xFFu;
-        if (tg && r < (uint32_t)R) {
-          const uint32_t pxy = O.rp[4 * w + b];
-          const uint32_t dxy = O.dst[(tg - 1u) % C::DP];   // x << 8 | y << 24 (| 0x00FF00FF)
-          im[Q0 + 4 * r] = (uint8_t)(pxy & 0xFFu);
-          im[Q0 + 4 * r + 1] = (uint8_t)(pxy >> 16);
-          im[Q0 + 4 * r + 2] = (uint8_t)(dxy >> 8);
-          im[Q0 + 4 * r + 3] = (uint8_t)(dxy >> 24);
-          ++r;
-        }
-      }
-      if (w == C::PW - 1)      // fewer than R active slots never occurs after reset/step; keep rows defined
-        for (; r < (uint32_t)R; ++r)
-          im[Q0 + 4 * r] = im[Q0 + 4 * r + 1] = im[Q0 + 4 * r + 2] = im[Q0 + 4 * r + 3] = 0;
-    }
-  }
+  if (mine) obs_image_requests<C, OBS_EB>(O, el, part);
   __syncthreads();
   const uint32_t per_env = (uint32_t)na * L;
   if (xfrag)   // the group's rows are whole 32-row tiles (OBS_EB * na % 32 == 0, checked on the host)
@@ -2354,17 +2416,11 @@ __global__ __launch_bounds__(BT) void k_observe(const uint32_t* __restrict__ sta
                                                               reinterpret_cast<f32x4*>(out), nenv, per_env >> 2, tid,
                                                               qlo, qhi);
   } else {
-    const uint32_t total = nenv * per_env;
-    const uint32_t magic = 0xFFFFFFFFu / per_env + 1u;
-    for (uint32_t o = tid; o < total; o += BT) {
-      const uint32_t el1 = __umulhi(o, magic);
-      const uint32_t k = o - el1 * per_env;
-      const uint32_t lim = O.lim[el1];
-      const uint8_t* sb = reinterpret_cast<const uint8_t*>(O.src[lim >> 31]);
-      out[o] = k < (lim & 0x7FFFFFFFu) ? (float)O.img[el1][sb[k]] : 0.0f;
-    }
+    stream_rows_scalar<C, OBS_EB>(O, out, nenv, per_env, tid);
   }
 }
+
+#include "replay.h"
 
 // ----------------------------------------------------------------------------- fused sampler step
 // The sampler route (wh_sampler_step: device policy + step + auto-reset, then the observation rows)
@@ -2779,6 +2835,8 @@ struct Kernels {
   void (*reset)(ResetParams);
   void (*observe[4])(const uint32_t*, int64_t, int, const uint32_t*, float*, int, uint4*);   // kObsEB[i] envs per WG
   void (*observe_chunk)(const uint32_t*, int64_t, int, const uint32_t*, float*, int, uint4*);   // kObsChunk float4s per WG
+  void (*replay_put)(PutParams);
+  void (*replay_gather[4])(GatherParams);   // kObsEB[i] samples per WG (the instances the gather uses: 0, 2, 3)
   int tblw, nv;
 };
 
@@ -2835,6 +2893,11 @@ Kernels make_kernels() {
   k.observe[2] = k_observe<C, kObsEB[2]>;
   k.observe[3] = k_observe<C, kObsEB[3]>;
   k.observe_chunk = kObsChunk > 0 ? k_observe<C, kObsEB[0], kObsChunk> : nullptr;
+  k.replay_put = k_replay_put<C>;
+  k.replay_gather[0] = k_replay_gather<C, kObsEB[0]>;
+  k.replay_gather[1] = nullptr;
+  k.replay_gather[2] = k_replay_gather<C, kObsEB[2]>;
+  k.replay_gather[3] = k_replay_gather<C, kObsEB[3]>;
   k.tblw = C::TBLW;
   k.nv = C::NV;
   return k;
@@ -3390,6 +3453,79 @@ int wh_vector_step_wide(const wh_config* cfg, int64_t B, uint32_t* state, const 
   const int rc = wh_abi::vector_step_call(&c, cfg, B, state, actions, nullptr, 0, mask, rewards, dones, obs, nullptr,
                                           false, stats, autoreset, variable_n, seed, env_offset, lanes);
   return rc ? rc : vector_step(c, stream);
+}
+
+// ---- replay ring (csrc/replay.h).  abi_args.h has checked the call; B > 0 (and M > 0) here.
+int wh_replay_put(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t slot, int32_t stage,
+                  const uint32_t* state, const int32_t* actions, const float* rewards, const uint8_t* dones,
+                  void* stream) {
+  Geometry g;
+  int rc = wh_abi::replay_put_call(&g, cfg, B, ring, slot, stage, state, actions, rewards, dones);
+  if (rc) return rc;
+  const Kernels* k = pick(g);
+  if (!k) return WH_ENOTSUP;
+  if (B == 0) return WH_OK;
+  const int64_t step = slot * B;
+  PutParams a{state, ring->states + (2 * step + (int64_t)stage * B) * g.words, B, g.words, g.NA,
+              stage == 0 ? actions : nullptr, stage == 0 ? ring->actions + step * g.NA : nullptr,
+              stage == 1 ? rewards : nullptr, stage == 1 ? ring->rewards + step * g.NA : nullptr,
+              stage == 1 ? dones : nullptr, stage == 1 ? ring->dones + step : nullptr};
+  hipLaunchKernelGGL(k->replay_put, grid_for(B), dim3(BT), 0, (hipStream_t)stream, a);
+  return hip_err(hipGetLastError());
+}
+
+int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t filled, int64_t M,
+                     const int64_t* idx, uint64_t seed, uint64_t draw, const wh_replay_batch* batch, void* stream) {
+  Geometry g;
+  int rc = wh_abi::replay_gather_call(&g, cfg, B, ring, filled, M, batch);
+  if (rc) return rc;
+  const Kernels* k;
+  const uint32_t* tab;
+  const bool empty = B == 0 || M == 0;
+  rc = locate(g, empty ? 0 : B, stream, &k, &tab);
+  if (rc || empty) return rc;
+  const bool frags = batch->xfrag || batch->next_xfrag;
+  // samples per workgroup: k_observe's choice for these rows (observe_launch), among the instances
+  // built here; the fragment operand needs whole 32-row tiles per workgroup
+  const int row_bytes = 4 * g.NA * g.L;
+  int sel = row_bytes <= 1024 ? 3 : (row_bytes <= 4096 ? 2 : 0);
+  if (frags && (kObsEB[sel] * g.NA) % 32 != 0) sel = 3;
+  const int eb = kObsEB[sel];
+  const int64_t groups = (M + eb - 1) / eb;
+  const bool next = batch->next_obs || batch->next_xfrag || batch->next_state;
+  if (groups * 2 > 0x7FFFFFFF) return WH_EINVAL;
+  GatherParams a{};
+  a.states = ring->states;
+  a.r_actions = ring->actions;
+  a.r_rewards = ring->rewards;
+  a.r_dones = ring->dones;
+  a.B = B;
+  a.filled = filled;
+  a.M = M;
+  a.idx = idx;
+  a.k0 = (uint32_t)(seed & 0xFFFFFFFFu);
+  a.k1 = (uint32_t)(seed >> 32);
+  a.d0 = (uint32_t)(draw & 0xFFFFFFFFu);
+  a.d1 = (uint32_t)(draw >> 32);
+  a.na = g.NA;
+  a.words = g.words;
+  a.quads = (g.NA * g.L) % 4 == 0;
+  a.groups = (unsigned)groups;
+  a.tables = tab;
+  a.obs[0] = batch->obs;
+  a.obs[1] = batch->next_obs;
+  a.xfrag[0] = static_cast<uint4*>(batch->xfrag);
+  a.xfrag[1] = static_cast<uint4*>(batch->next_xfrag);
+  a.state[0] = batch->state;
+  a.state[1] = batch->next_state;
+  a.actions = batch->actions;
+  a.rewards = batch->rewards;
+  a.dones = batch->dones;
+  a.n = batch->n;
+  a.idx_out = batch->idx_out;
+  hipLaunchKernelGGL(k->replay_gather[sel], dim3((unsigned)(groups * (next ? 2 : 1))), dim3(BT), 0,
+                     (hipStream_t)stream, a);
+  return hip_err(hipGetLastError());
 }
 
 }  // extern "C"

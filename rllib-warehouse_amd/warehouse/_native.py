@@ -44,7 +44,8 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_observe_x", "wh_mlp_forward_x",
            "wh_check_read", "wh_rollout_prepare", "wh_launch_run", "wh_launch_run_timed", "wh_launch_free",
            "wh_sampler_step", "wh_sampler_step_to", "wh_sampler_rollout", "wh_vector_step_x",
-           "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide")
+           "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide",
+           "wh_replay_put", "wh_replay_gather")
 
 
 class WhConfig(ctypes.Structure):
@@ -86,6 +87,17 @@ class WhEpisodeStats(ctypes.Structure):
         ("return_min", ctypes.c_void_p),
         ("return_max", ctypes.c_void_p),
     ]
+
+
+class WhReplayRing(ctypes.Structure):
+    _fields_ = [("states", ctypes.c_void_p), ("actions", ctypes.c_void_p), ("rewards", ctypes.c_void_p),
+                ("dones", ctypes.c_void_p), ("capacity", ctypes.c_int64)]
+
+
+class WhReplayBatch(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in
+                ("obs", "next_obs", "xfrag", "next_xfrag", "state", "next_state", "actions", "rewards", "dones",
+                 "n", "idx_out")]
 
 
 WH_MLP_BF16 = 0
@@ -171,6 +183,9 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_step_wide.argtypes = [_CFG, _I64, _P, _P, _P, _P, _P, _P, _U64, _I64, _I32, _P]
     S.wh_rollout_wide.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _I32, _P]
     S.wh_vector_step_wide.argtypes = [_CFG, _I64, _P, _P, _P, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _I32, _P]
+    S.wh_replay_put.argtypes = [_CFG, _I64, ctypes.POINTER(WhReplayRing), _I64, _I32, _P, _P, _P, _P, _P]
+    S.wh_replay_gather.argtypes = [_CFG, _I64, ctypes.POINTER(WhReplayRing), _I64, _I64, _P, _U64, _U64,
+                                   ctypes.POINTER(WhReplayBatch), _P]
     _MD = ctypes.POINTER(WhMlpDesc)
     S.wh_mlp_query.argtypes = [_MD, ctypes.POINTER(ctypes.c_int64)]
     S.wh_mlp_pack.argtypes = [_MD] + [_P] * 7
