@@ -156,6 +156,15 @@ constexpr bool kHoistPolicy = true;
 #else
 constexpr bool kHoistPolicy = false;
 #endif
+// k_step's fused greedy loop is rotated: the request walk of step t + 1 (policy_walk: nine dependent
+// LDS lookups) is issued right after step t's regeneration, and its results cross the back-edge in
+// registers, so their latency is behind the loop branch instead of in front of the policy's distance
+// tests; a reset redoes the walk.  -DWH_NO_WALK_ROTATE: the walk at the head of its own step (A/B).
+#ifndef WH_NO_WALK_ROTATE
+constexpr bool kWalkRotate = true;
+#else
+constexpr bool kWalkRotate = false;
+#endif
 #ifndef WH_NO_REGEN_SKIP
 constexpr bool kRegenSkip = true;
 #else
@@ -832,6 +841,36 @@ __device__ __forceinline__ void reset_injected(Regs<C>& s, Lds<C>& L, int64_t e,
 }
 
 // ----------------------------------------------------------------------------- policy
+// The greedy policy's request walk: the (at most R) open requests in ascending pickup order
+// (core.py:409-418) as packed keys rp[] / tg[] for v_sad_hi_u8.  Index P of the tables is a
+// sentinel (far-away cell, null-cell tag) that fills missing slots; after a reset every slot is
+// the sentinel, so every agent's "nearest request" is the null cell, which is where the
+// reference's reset observation sends the greedy solver (availability 0, core.py:233-236).
+// Reads only the request mask and the fresh bit, so the fused step loop can run it for step t + 1
+// as soon as step t's regeneration is done (run_steps_fast, kWalkRotate).
+template <class C>
+__device__ __forceinline__ void policy_walk(const Regs<C>& s, const Lds<C>& L, uint32_t (&rp)[C::R],
+                                            uint32_t (&tg)[C::R]) {
+  const uint32_t mf = 0u - ((s.hdr >> 24) & 1u);
+  uint32_t mlo = bop3<~TA & TB>(mf, (uint32_t)s.am, 0u);
+  uint32_t mhi = bop3<~TA & TB>(mf, (uint32_t)(s.am >> 32), 0u);
+#pragma unroll
+  for (int r = 0; r < C::R; ++r) {
+    uint32_t flo, fhi;
+    asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(mlo));   // 0xFFFFFFFF when empty
+    asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(mhi));
+    const uint32_t j = __builtin_elementwise_min(
+        __builtin_elementwise_min(flo, __builtin_elementwise_add_sat(fhi, 32u)), (uint32_t)C::P);
+    const uint2 v = L.rtag(j);
+    rp[r] = v.x;
+    tg[r] = v.y;
+    uint64_t m = ((uint64_t)mhi << 32) | mlo;
+    m &= m - 1ull;
+    mlo = (uint32_t)m;
+    mhi = (uint32_t)(m >> 32);
+  }
+}
+
 // baseline/solvers.py:27-58 evaluated on the state, producing unit steps d (packed i16 pairs):
 // availability 0 (fresh reset, or carrying) -> head for the own delivery target (the null cell
 // after reset), else for the nearest open request by Manhattan distance, first (lowest pickup
@@ -840,9 +879,12 @@ __device__ __forceinline__ void reset_injected(Regs<C>& s, Lds<C>& L, int64_t e,
 // EFF: random moves are returned as the step they take (off-grid coordinates kept, core.py:282-287),
 // so a step loop can add them without the clamp (step_env<CLAMP = false>); wh_policy reports the
 // drawn action itself (EFF = false), as solvers.py:44-45 returns action_space.sample().
-template <class C, int POLICY, bool EFF = false>
+// WALKED: rp[] / tg[] hold the state's request walk already (policy_walk); else it is done here.
+template <class C, int POLICY, bool EFF = false, bool WALKED = false>
 __device__ __forceinline__ void policy_steps(const Regs<C>& s, const Lds<C>& L, const Keys& k,
-                                             uint32_t gid, float p, uint32_t (&d)[C::NAM]) {
+                                             uint32_t gid, float p, uint32_t (&d)[C::NAM],
+                                             uint32_t (*walk_rp)[C::R] = nullptr,
+                                             uint32_t (*walk_tg)[C::R] = nullptr) {
   const uint32_t t = s.hdr & 0xFFFFu;
   if (POLICY == POL_RANDOM) {
 #pragma unroll
@@ -856,28 +898,15 @@ __device__ __forceinline__ void policy_steps(const Regs<C>& s, const Lds<C>& L, 
     }
   } else {
     WH_PHASE_MARK(policy_rtag);
-    // Open requests in ascending pickup order (core.py:409-418).  Index P of the tables is a
-    // sentinel (far-away cell, null-cell tag) that fills missing slots; after a reset every slot is
-    // the sentinel, so every agent's "nearest request" is the null cell, which is where the
-    // reference's reset observation sends the greedy solver (availability 0, core.py:233-236).
-    const uint32_t mf = 0u - ((s.hdr >> 24) & 1u);
-    uint32_t mlo = bop3<~TA & TB>(mf, (uint32_t)s.am, 0u);
-    uint32_t mhi = bop3<~TA & TB>(mf, (uint32_t)(s.am >> 32), 0u);
     uint32_t rp[C::R], tg[C::R];
+    if constexpr (WALKED) {
 #pragma unroll
-    for (int r = 0; r < C::R; ++r) {
-      uint32_t flo, fhi;
-      asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(mlo));   // 0xFFFFFFFF when empty
-      asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(mhi));
-      const uint32_t j = __builtin_elementwise_min(
-          __builtin_elementwise_min(flo, __builtin_elementwise_add_sat(fhi, 32u)), (uint32_t)C::P);
-      const uint2 v = L.rtag(j);
-      rp[r] = v.x;
-      tg[r] = v.y;
-      uint64_t m = ((uint64_t)mhi << 32) | mlo;
-      m &= m - 1ull;
-      mlo = (uint32_t)m;
-      mhi = (uint32_t)(m >> 32);
+      for (int r = 0; r < C::R; ++r) {
+        rp[r] = (*walk_rp)[r];
+        tg[r] = (*walk_tg)[r];
+      }
+    } else {
+      policy_walk<C>(s, L, rp, tg);
     }
     WH_PHASE_MARK(policy_agents);
 #pragma unroll
@@ -1316,6 +1345,23 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
           // pin the hoisted block to this basic block (LLVM would sink it back to its only use)
           if constexpr (HOIST) asm volatile("" : "+v"(rblk0.x), "+v"(rblk0.y), "+v"(rblk0.z), "+v"(rblk0.w));
         };
+        // did an agent that shares a cell move?  (positions are final after the move loop: a pickup
+        // changes target bytes only)
+        auto shared_moved = [&]() {
+          uint32_t acc = 0;
+#pragma unroll
+          for (int i = 0; i < C::NAM; ++i)
+            acc |= (s.ag[i] ^ pp[i]) & (XY16 & (uint32_t)__builtin_amdgcn_sbfe((int)lg->cm, (uint32_t)i, 1u));
+          lg->rebuild = lg->rebuild || acc != 0u;
+        };
+        // Where the reverse-key loop runs exactly for the waves with shared cells, that test is made
+        // on its (rare) side of the branch, so the common path has no branch between the pickup
+        // tail and regeneration item 0 and the two are scheduled as one block.
+#if defined(WH_FORCE_NOREV) || defined(WH_NO_PICK_MERGE)   // (A/B: the test after the pickup tail)
+        constexpr bool CM_IN_REV = false;
+#else
+        constexpr bool CM_IN_REV = LAZY && C::NAM <= kRevSplitMaxNam;
+#endif
         // REV: the exact loop for waves with co-located agents (reverse keys in the two-key form; in
         // the one-key form every stay's key flipped), else the loop for waves without any (no reverse
         // keys / every key flipped).  From kRevSplitMaxNam agents on a single (exact) loop.
@@ -1329,6 +1375,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
           if (LAZY && __lane_id() == 0) atomicAdd(&g_wh_revcount[0], 1ull);
 #endif
           move_loop(std::true_type{});
+          if constexpr (CM_IN_REV) shared_moved();
         } else {
 #ifdef WH_COUNT_REV
           if (__lane_id() == 0) atomicAdd(&g_wh_revcount[1], 1ull);
@@ -1346,12 +1393,8 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
           for (int i = (C::NAM > 3 * PD ? C::NAM - 3 * PD : 0); i < C::NAM; ++i) pick(i, cp[i], tb[i], dst[i]);
         }
         looked = true;
-        if (LAZY && WH_RARE(__any(lg->cm != 0u))) {   // did an agent that shares a cell move?
-          uint32_t acc = 0;
-#pragma unroll
-          for (int i = 0; i < C::NAM; ++i)
-            acc |= (s.ag[i] ^ pp[i]) & (XY16 & (uint32_t)__builtin_amdgcn_sbfe((int)lg->cm, (uint32_t)i, 1u));
-          lg->rebuild = lg->rebuild || acc != 0u;
+        if constexpr (LAZY && !CM_IN_REV) {
+          if (WH_RARE(__any(lg->cm != 0u))) shared_moved();
         }
       }
     }
@@ -1888,6 +1931,11 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
   uint8_t* drow = a.dones + (e - tid);
   const int64_t rstride = a.B * C::NAM;
   LazyGrid lg{true, 0u};   // the grid starts empty (k_step)
+  // ROT: the step's request walk was made at the end of the previous step (kWalkRotate); the first
+  // step's here, and a reset's -- which replaces the request mask and sets `fresh` -- after it
+  constexpr bool ROT = kWalkRotate && POLICY == POL_GREEDY && !kAblationBuild;
+  [[maybe_unused]] uint32_t wrp[C::R], wtg[C::R];
+  if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);
   for (int stp = 0; stp < a.steps; ++stp) {
     uint32_t d[C::NAM];
     if constexpr (POLICY == POL_EXTERNAL) {   // (wh_vector_step's fast case: one step)
@@ -1899,6 +1947,8 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
     } else if (ablate & 1) {
 #pragma unroll
       for (int i = 0; i < C::NAM; ++i) d[i] = L.mv((uint32_t)((i + stp) % 9));
+    } else if constexpr (ROT) {
+      policy_steps<C, POLICY, true, true>(s, L, k, gid, a.p, d, &wrp, &wtg);
     } else {
       policy_steps<C, POLICY, POLICY == POL_GREEDY && !kAblationBuild>(s, L, k, gid, a.p, d);
     }
@@ -1911,6 +1961,7 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
     const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, kLazyGrid>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
                                                 (uint32_t)a.T, (uint32_t)a.W, rew, nullptr, tid, ablate, &lg,
                                                 kHoistPolicy ? &rb : nullptr);
+    if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);   // the next step's (redone below after a reset)
     if (!(ablate & 64)) {
       store_row<C>(rrow + tid * C::NAM, rew);
       drow[tid] = done ? 1 : 0;
@@ -1949,6 +2000,7 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
         for (int y = 0; y < C::D; ++y) L.occ[y][tid] = 0u;
         lg.rebuild = true;
       }
+      if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);   // of the states the resets left
     }
     WH_CHECK_ENV(s, L, e, tid);
   }
