@@ -46,14 +46,8 @@ constexpr int BT = 256;  // lanes (= envs) per workgroup
 // differ between the two lanes -- the move loop's target-byte lookups, the pickup clears and the
 // regeneration stores.  32-bit cells (the upper half unused) give every lane of a group its own
 // bank for twice the LDS, and measured slower anyway (Medium-8 +0.3 %, Large-16 +0.4 % per
-// 200-step launch, profiles/r05_occ_ab.txt; round 4 the same), so the cells stay 16-bit;
-// -DWH_PKP32 selects 32-bit cells (A/B).
-#if defined(WH_PKP32)
-constexpr bool kPkWide = true;
-#else
-constexpr bool kPkWide = false;
-#endif
-using PkCell = std::conditional_t<kPkWide, uint32_t, uint16_t>;
+// 200-step launch, profiles/r05_occ_ab.txt; round 4 the same), so the cells stay 16-bit.
+using PkCell = uint16_t;
 constexpr uint32_t PKW = sizeof(PkCell);
 constexpr uint32_t ROWB = PKW * BT;   // bytes per pickup-point row of the LDS pickup plane
 
@@ -66,13 +60,6 @@ constexpr bool kAblationBuild = true;    // ablation moves are arbitrary: keep t
 constexpr bool kAblationBuild = false;
 #endif
 
-// A/B switches of the fused fast path (tools/anat_ab.sh): -DWH_NO_BIAS keeps plain occupancy-row
-// addressing, -DWH_NO_REGEN_HOIST computes the regeneration's Philox block inside the regeneration.
-#ifndef WH_NO_BIAS
-constexpr bool kBiasAddr = true;
-#else
-constexpr bool kBiasAddr = false;
-#endif
 // -DWH_OBS_EB0=<n>: envs per workgroup of the observation kernel for the widest f32 rows (Large)
 #ifndef WH_OBS_EB0
 #define WH_OBS_EB0 4
@@ -96,51 +83,15 @@ constexpr int kObsChunk = WH_OBS_CHUNK;
 // Medium's rows (nontemporal: observe +10 %, sampler step +24 %).  The fragment operand plain: stored
 // nontemporal it is written 5-11 % faster but the policy network then reads it from HBM instead of
 // the last-level cache, and the policy route is 1 % slower at Medium-8 (no gain at Large-16).
-// -DWH_OBS_NT / -DWH_OBS_NO_NT: every single-step row store nontemporal / none (A/B switches).
 template <class C>
 constexpr bool rows_nt() {
-#if defined(WH_OBS_NT)
-  return true;
-#elif defined(WH_OBS_NO_NT)
-  return false;
-#else
   return C::NAM * C::L * 4 <= 1024 || C::NAM * C::L * 4 > 4096;
-#endif
 }
-constexpr bool kFragNT = false;
 
 #ifndef WH_REV_SPLIT_MAX_NAM   // agent counts up to which the move loop has the no-reverse-key variant
 #define WH_REV_SPLIT_MAX_NAM 9
 #endif
-#ifndef WH_UKEY_MIN_NAM        // agent counts from which the ascending move loop uses one key per move
-#define WH_UKEY_MIN_NAM 0      // (A/B builds: 99 = the two-key form with its reverse-key split)
-#endif
-constexpr int kUKeyMinNam = WH_UKEY_MIN_NAM;
-#ifndef WH_BIAS_MAX_NAM
-#define WH_BIAS_MAX_NAM 64
-#endif
-constexpr int kRevSplitMaxNam = WH_REV_SPLIT_MAX_NAM, kBiasMaxNam = WH_BIAS_MAX_NAM;
-#ifndef WH_NO_REGEN_HOIST
-constexpr bool kRegenHoist = true;
-#else
-constexpr bool kRegenHoist = false;
-#endif
-// Regeneration targets of items 1 and 2 by skipping the earlier items' targets (a compare-add each)
-// instead of a rank selection on a used-target mask; the mask is built only from item 3 on.  Same
-// values.  -DWH_NO_REGEN_SKIP: the mask for every item (A/B).
-// The regeneration's first Philox block is computed in the fused step's policy block (its ten rounds
-// fill that block's issue gaps) rather than inside the move loop's: -0.5 % per step at Medium-8 and
-// Large-16 (profiles/r05_step3_ab.txt).  -DWH_NO_HOIST_POLICY: inside the move loop (A/B).
-// The ascending move loop reads agent s's occupancy word kOccAhead turns early and corrects it in
-// registers for the agents that moved in between (4 VALU per corrected agent), so the LDS latency
-// -- which queues behind the turn's own lookups, lgkmcnt being in order -- is covered by that many
-// turns of work.  Two turns measured slower than one (Medium-8 +2.4 %, Large-16 +3.1 % per 200-step
-// launch, profiles/r05_occ_ab.txt: the second correction's VALU cost more than the wait it hid), so
-// the default is one; -DWH_OCC_AHEAD=2 (A/B).
-#ifndef WH_OCC_AHEAD
-#define WH_OCC_AHEAD 1
-#endif
-constexpr int kOccAhead = WH_OCC_AHEAD;
+constexpr int kRevSplitMaxNam = WH_REV_SPLIT_MAX_NAM;
 // Turns between the move loop's dependent pickup lookups (cell -> point row, point -> target byte,
 // target -> delivery cell, then the decision): each lookup is issued kPickDist turns after the one
 // it depends on, so its LDS latency is covered by that many turns of the serial chain.  Two turns:
@@ -150,12 +101,6 @@ constexpr int kOccAhead = WH_OCC_AHEAD;
 #define WH_PICK_DIST 2
 #endif
 constexpr int kPickDist = WH_PICK_DIST;
-static_assert(kOccAhead == 1 || kOccAhead == 2, "occupancy read distance");
-#ifndef WH_NO_HOIST_POLICY
-constexpr bool kHoistPolicy = true;
-#else
-constexpr bool kHoistPolicy = false;
-#endif
 // k_step's fused greedy loop is rotated: the request walk of step t + 1 (policy_walk: nine dependent
 // LDS lookups) is issued right after step t's regeneration, and its results cross the back-edge in
 // registers, so their latency is behind the loop branch instead of in front of the policy's distance
@@ -164,11 +109,6 @@ constexpr bool kHoistPolicy = false;
 constexpr bool kWalkRotate = true;
 #else
 constexpr bool kWalkRotate = false;
-#endif
-#ifndef WH_NO_REGEN_SKIP
-constexpr bool kRegenSkip = true;
-#else
-constexpr bool kRegenSkip = false;
 #endif
 
 constexpr uint32_t IDLE = 0xFF00FF00u;    // delivery-target bytes of an idle agent
@@ -179,14 +119,7 @@ constexpr uint32_t XY16 = 0x00FF00FFu;    // position bytes of an agent word
 // conflicts).  Skewed: byte 4x + 132y (one v_dot4_u32_u8 of the agent word), bank (x + y) mod 32.
 // Same-box A/B (profiles/r05_step3_ab.txt): Large-16 -1.6 % per step (-2.9 % with the policy-block
 // Philox hoist), Medium-8 +3 % -- so the skewed table is used from D = 20 (Large) on.
-// -DWH_CELL_SKEW / -DWH_NO_CELL_SKEW force it on / off for every geometry (A/B).
-#if defined(WH_CELL_SKEW)
-__host__ __device__ constexpr bool cell_skew(int) { return true; }
-#elif defined(WH_NO_CELL_SKEW)
-__host__ __device__ constexpr bool cell_skew(int) { return false; }
-#else
 __host__ __device__ constexpr bool cell_skew(int D) { return D >= 20; }
-#endif
 __host__ __device__ constexpr int cell_bytes(int D) { return cell_skew(D) ? 132 * D : 256 * D; }
 __host__ __device__ constexpr int cell_index(int x, int y, int D) { return cell_skew(D) ? 4 * x + 132 * y : (x | (y << 8)); }
 
@@ -322,23 +255,9 @@ __device__ __forceinline__ uint32_t pk_min_i16(uint32_t a, uint32_t b) {
   asm("v_pk_min_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
-__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
-  typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(ushort2v, a),
-                                                                __builtin_bit_cast(ushort2v, b)));
-}
 __device__ __forceinline__ uint32_t pk_sub_i16(uint32_t a, uint32_t b) {
   uint32_t r;
   asm("v_pk_sub_i16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
-// dx * dy of a packed (dx, dy) i16 pair in ONE op, in both halves: v_pk_mul_lo_u16 of the pair with
-// itself, the second operand's halves swapped by op_sel (a builtin dot2 costs a v_alignbit and a
-// zeroed accumulator on top).
-__device__ __forceinline__ uint32_t mul_swap(uint32_t d) {
-  uint32_t r;
-  asm("v_pk_mul_lo_u16 %0, %1, %1 op_sel:[0,1] op_sel_hi:[1,0]" : "=v"(r) : "v"(d));
   return r;
 }
 
@@ -360,12 +279,7 @@ __device__ __forceinline__ uint32_t action_of(uint32_t d) {
 
 // Rare wave-uniform branches of the step loop (expiry pass, grid rebuild, resets, random moves): marked
 // cold so that block placement keeps their code out of the hot path's instruction stream.
-// -DWH_NO_COLD: no annotation (A/B).
-#ifndef WH_NO_COLD
 #define WH_RARE(x) __builtin_expect(!!(x), 0)
-#else
-#define WH_RARE(x) (x)
-#endif
 
 // Phase labels in the device assembly for instruction-count analysis (`make asm` defines
 // WH_PHASE_MARKS).  Not in the library: each label is an asm volatile with a memory clobber, a
@@ -393,8 +307,7 @@ struct Lds {
   uint32_t occ[C::D][BT];        // occupancy row y: bit x
   // Pickup point j of lane tid: low byte = request target + 1 (0 = none), high byte = expiry step
   // (low 8 bits).  Row P is scratch: predicated stores of lanes with nothing to write go there.
-  // One cell per (point, lane) (PkCell: 32-bit, the upper half unused, so that no two lanes of a
-  // 32-lane group share a bank) makes every per-point access a single ds op whose address is
+  // One cell per (point, lane) makes every per-point access a single ds op whose address is
   // j * BT + tid, and keeps the pickup table out of the VGPRs.
   PkCell pkp[C::P + 1][BT];
   // Agent words when processing in action-dict order; afterwards the reward-row staging area.
@@ -989,13 +902,8 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
   const uint32_t n = (s.hdr >> 16) & 0xFFu;
   uint32_t t = s.hdr & 0xFFFFu;
   uint32_t rewm[C::NAM];   // reward masks: all-ones = 1.0f
-  constexpr bool HOIST = LAZY && !INJ && kRegenHoist && !kHoistPolicy;   // (see the move phase)
-  uint4 rblk0 = make_uint4(0u, 0u, 0u, 0u);
-  bool hoisted = false;
-  if (pre_rblk) {   // computed by the caller ahead of the policy (kHoistPolicy)
-    rblk0 = *pre_rblk;
-    hoisted = true;
-  }
+  // the regeneration's Philox block 0, where the caller computed it ahead of the policy (run_steps_fast)
+  const uint4 rblk0 = pre_rblk ? *pre_rblk : make_uint4(0u, 0u, 0u, 0u);
 
   if (phase != PH_REGEN) {
     t = (t + 1u) & 0xFFFFu;                                 // core.py:267
@@ -1062,10 +970,6 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 
     // ---- move + collision, sequential in action-dict order (core.py:275-300)
     WH_PHASE_MARK(move);
-    // The fused rollout's regeneration almost always draws (some lane of the wave reopens a point
-    // on nearly every step), so its first Philox block -- a chain of ten dependent rounds -- is
-    // computed inside the move loop's basic block, where the scheduler fills the serial chain's
-    // issue gaps with it, instead of on its own after the pickups.
     uint32_t cp[C::NAM], tb[C::NAM], dst[C::NAM];   // pickup lookups (core.py:309-329): cell_row,
                                                     // target byte, delivery cell
     bool looked = false;
@@ -1091,11 +995,6 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
       clr[i] = msel(m, cpv, (uint32_t)(C::P + 1));
       rewm[i] = m;
     };
-#ifndef WH_NO_PICK_IN_LOOP   // (A/B builds: -DWH_NO_PICK_IN_LOOP decides after the move loop)
-    constexpr bool PICK_IN_LOOP = true;
-#else
-    constexpr bool PICK_IN_LOOP = false;
-#endif
     if (!(ablate & 2)) {
       // The grid is rebuilt as {live agents' cells} (core.py:275-276) by OR-ing the cells into
       // what the previous step left, which is always a subset of them (a set bit is an arrival
@@ -1150,10 +1049,9 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         lg->cm = cm;
         lg->rebuild = false;
       }
-      uint32_t rk[C::NAM], xk[C::NAM];   // ascending path: reverse key, crossing pair
       if (ORDERED) {   // drop-in single env / BaseEnv: entries in action-dict order, records in LDS
-        // Forbidden moves (core.py:293-297) by the one-key-per-move form of the ascending loop (UKEY,
-        // below): a move p -> c is keyed by its direction and its undirected edge / square / cell
+        // Forbidden moves (core.py:293-297) by the ascending loop's one key per move (below): a move
+        // p -> c is keyed by its direction and its undirected edge / square / cell
         // (u = p + c per coordinate), and an accepted move forbids exactly the moves with its u and
         // another direction (an accepted stay: every later stay on its cell, via a flipped low bit).
         // 16 bits per key: (dx + 1) | (dy + 1) << 2 | xsum << 4 | ysum << 10, so entry k is blocked iff
@@ -1205,15 +1103,19 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
       } else {
         // Ascending agent order.  Every agent moves only on its own turn, so all candidate cells
         // are known up front.  The occupancy word for agent s+1 is read one turn early (before
-        // agent s updates the grid) and corrected in registers for agent s's clear/set, so no
-        // LDS round trip sits on the serial chain; agent s's pickup lookups (cell -> point, point
-        // -> target byte, target -> cell) are issued on turns s, s+1, s+2.
+        // agent s updates the grid) and corrected in registers for agent s's clear/set (4 VALU), so
+        // the LDS latency -- which queues behind the turn's own lookups, lgkmcnt being in order --
+        // is covered by a turn of work and no LDS round trip sits on the serial chain.  Reading two
+        // turns early measured slower (Medium-8 +2.4 %, Large-16 +3.1 % per 200-step launch,
+        // profiles/r05_occ_ab.txt: the second correction's VALU cost more than the wait it hid).
+        // Agent s's pickup lookups (cell -> point, point -> target byte, target -> cell) are issued
+        // kPickDist turns apart, from turn s on.
         // BIAS (greedy steps, never off the grid): positions carry the lane id in bits 8-15
         // (x | lane << 8 | y << 16), so `q >> 6` is the byte offset of the occupancy word
         // occ[y][lane] (y * 1024 + lane * 4; x < 32) -- one shift per LDS address instead of a
-        // field extract and a shift-or.  Equality tests, x-bit selects and the square key's
-        // packed minimum are unaffected (every position of a lane carries the same lane bits).
-        constexpr bool BIAS = !CLAMP && kBiasAddr && C::NAM <= kBiasMaxNam;
+        // field extract and a shift-or.  Equality tests, x-bit selects and the move key's
+        // coordinate sums are unaffected (every position of a lane carries the same lane bits).
+        constexpr bool BIAS = !CLAMP;
         static_assert(BT * 4 == 1024 && C::D <= 32, "occ[y][lane] = byte y << 10 | lane << 2");
         const uint32_t lbias = BIAS ? ((uint32_t)tid & 255u) << 8 : 0u;
         auto occ_at = [&](uint32_t q) -> uint32_t* {
@@ -1231,104 +1133,62 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         // Predicates are kept in bit 31 of VGPRs (x31 names) and selects are v_bitop3 with
         // 0 / all-ones masks (m names): no VCC round trips on the serial chain.
         //
-        // Forbidden moves (core.py:293-297): the reverse of every accepted move, matched as an
-        // ordered (from, to) key, and for accepted diagonals the two crossing moves.  A move's
-        // square key is the low corner of the 2x2 square it spans plus dx*dy in the top byte
-        // (0x01 one diagonal, 0xFF the other, 0 straight or stay); "either crossing move of i" is
-        // exactly "same square, opposite diagonal", i.e. square key == i's with the top byte
-        // flipped (^ 0xFE000000: 0x01 <-> 0xFF), which no straight move's key (0) ever equals.
-        // REV = false drops the reverse keys: a later agent can stand on the cell an accepted move
-        // went to only if that cell had been freed by a co-located agent leaving it (the grid was
-        // rebuilt from every position, and a move is accepted only into a free cell), so without
-        // co-located agents in the lane no reverse key can ever match.  The lazy grid knows the
-        // lanes with shared cells (lg->cm, from the last rebuild; new sharing needs an existing
-        // one), so a wave with none of them tests the crossing keys only -- one xor per earlier
-        // agent, reduced three at a time, instead of two xors and a min3.
-        //
-        // UKEY: one key per move and ONE test per earlier agent, exact in every lane, so there is a
-        // single loop variant.  A unit move p -> c is keyed by its undirected edge or
-        // square, u = p + c per coordinate (x and y sums; a stay has both even, an axis move one odd,
-        // a diagonal both odd -- and both diagonals of a square share it), and by its direction
-        // (dx, dy) bytes: K = dx | dy << 8 | xsum << 16 | ysum << 24.  The moves an accepted move
-        // forbids (core.py:293-297) are exactly those with its u and another direction -- its
-        // reverse, and for a diagonal the two directions of the other diagonal -- so agent i is
-        // blocked iff some stored key S_j has 1 <= (K_i ^ S_j) <= 0xFFFF: one v_xad ((K ^ S) - 1)
-        // and half a v_min3 per pair against a cap of 0xFFFF.  An accepted stay adds its own key
+        // Forbidden moves (core.py:293-297): the reverse of every accepted move, and for accepted
+        // diagonals the two crossing moves.  One key per move and ONE test per earlier agent, exact
+        // in every lane.  A unit move p -> c is keyed by its undirected edge or square, u = p + c
+        // per coordinate (x and y sums; a stay has both even, an axis move one odd, a diagonal both
+        // odd -- and both diagonals of a square share it), and by its direction (dx, dy) bytes:
+        // K = dx | dy << 8 | xsum << 16 | ysum << 24.  The moves an accepted move forbids are
+        // exactly those with its u and another direction -- its reverse, and for a diagonal the
+        // two directions of the other diagonal -- so agent i is blocked iff some stored key S_j has
+        // 1 <= (K_i ^ S_j) <= 0xFFFF: one v_xad ((K ^ S) - 1) and half a v_min3 per pair against a
+        // cap of 0xFFFF.  An accepted stay adds its own key
         // (p, p) to the reference's set (it can be accepted where a co-located agent left the cell):
         // its stored key has the low bit flipped, so a later stay on that cell lands on 1.  A
         // rejected move stores ~0 (its high bytes never match: sums <= 62).  Same-box A/B against
-        // the two-key form below (reverse-key split): 200-step launches Large-16 -10 %, Medium-8
-        // -5 % (at Large the split variant made the step loop spill in its common path).
-        constexpr bool UKEY = C::NAM >= kUKeyMinNam;
+        // the earlier two-key form (an ordered reverse key and a crossing-square key per move, the
+        // reverse keys dropped for waves without co-located agents): 200-step launches Large-16
+        // -10 %, Medium-8 -5 % (at Large that form made the step loop spill in its common path).
+        // REV = false (a wave without co-located agents, below) stores every key as a stay's.
         uint32_t sk[C::NAM];
         auto move_loop = [&](auto rev_tag) {
           constexpr bool REV = decltype(rev_tag)::value;
-          if constexpr (HOIST) {   // (an opaque zero keeps LLVM from hoisting it above the branch)
-            uint32_t z;
-            asm volatile("v_mov_b32 %0, 0" : "=v"(z));
-            rblk0 = stream_block(k, gid ^ z, s.epi, t, PUR_REGEN, 0u);
-            hoisted = true;
-          }
-          // raws[s % kOccAhead]: agent s's row word, read kOccAhead turns early (before the
-          // updates of agents s - kOccAhead .. s - 1, which the turn applies in registers)
-          uint32_t raws[kOccAhead];
-#pragma unroll
-          for (int j = 0; j < kOccAhead; ++j) raws[j] = j < C::NAM ? *occ_at(cc[j < C::NAM ? j : 0]) : 0u;
+          uint32_t raw = *occ_at(cc[0]);   // agent sidx's row word, read before agent sidx - 1's update
           uint32_t mokh[C::NAM];   // accept masks of the agents already moved
 #pragma unroll
           for (int sidx = 0; sidx < C::NAM; ++sidx) {
             const uint32_t p = pp[sidx], c = cc[sidx], a = s.ag[sidx];
-            // occupied: bit c of the row word, corrected for the clear-then-set of each agent that
-            // moved after the word was read, in order
-            uint32_t occ31 = (uint32_t)__builtin_amdgcn_sbfe((int)raws[sidx % kOccAhead], c, 1);
-#pragma unroll
-            for (int j = sidx - kOccAhead; j < sidx; ++j) {
-              if (j < 0) continue;
+            // occupied: bit c of the row word, corrected for the clear-then-set of the agent that
+            // moved after the word was read
+            uint32_t occ31 = (uint32_t)__builtin_amdgcn_sbfe((int)raw, c, 1);
+            if (sidx >= 1) {
+              const int j = sidx - 1;
               const uint32_t set31 = (c ^ cc[j]) - 1u;   // bit 31: c == agent j's new cell
               const uint32_t clr31 = (c ^ pp[j]) - 1u;   // bit 31: c == agent j's old cell
               occ31 = bop3<(TA & TB) | (TC & ~(TA & TB))>(mokh[j], set31, bop3<TC & ~(TA & TB)>(mokh[j], clr31, occ31));
             }
-            // agent sidx + kOccAhead's word, before this turn's update
-            if (sidx + kOccAhead < C::NAM) raws[sidx % kOccAhead] = *occ_at(cc[sidx + kOccAhead < C::NAM ? sidx + kOccAhead : 0]);
+            // agent sidx + 1's word, before this turn's update
+            if (sidx + 1 < C::NAM) raw = *occ_at(cc[sidx + 1 < C::NAM ? sidx + 1 : 0]);
             const uint32_t dd = CLAMP ? pk_sub_i16(c, p) : dstep[sidx];
-            uint32_t ukey, kpr = 0;
-            uint32_t f = 0x7FFFFFFFu;   // unused key slots hold ~0: their xor is never 0
-            if constexpr (UKEY) {
-              kpr = __builtin_amdgcn_perm(as_u(as_s2(p) + as_s2(c)), dd, 0x06040200u);
-              f = 0xFFFFu;
+            const uint32_t kpr = __builtin_amdgcn_perm(as_u(as_s2(p) + as_s2(c)), dd, 0x06040200u);
+            uint32_t f = 0xFFFFu;
 #pragma unroll
-              for (int j = 0; j < sidx; ++j) f = min(f, (kpr ^ sk[j]) - 1u);
-              f -= 0xFFFEu;   // bit 31 of f - 1 below: blocked (f was < 0xFFFF)
-            } else {
-              ukey = pk_min_u16(p, c) + (mul_swap(dd) << 24);   // top byte dx*dy: 1, 0xFF, 0
-              if constexpr (REV) {
-                const uint32_t key = (p & XY16) | ((c & XY16) << 8);
-#pragma unroll
-                for (int j = 0; j < sidx; ++j) f = min(f, min(rk[j] ^ key, xk[j] ^ ukey));
-              } else {
-#pragma unroll
-                for (int j = 0; j < sidx; ++j) f = min(f, xk[j] ^ ukey);
-              }
-            }
+            for (int j = 0; j < sidx; ++j) f = min(f, (kpr ^ sk[j]) - 1u);
+            f -= 0xFFFEu;   // bit 31 of f - 1 below: blocked (f was < 0xFFFF)
             const uint32_t live31 = (uint32_t)sidx - n;                 // bit 31: sidx < n
             const uint32_t mok = sgn(bop3<TA & ~TB & ~TC>(live31, occ31, f - 1u));
             atomicAnd(occ_at(p), bop3<~(TA & TB)>(mok, 1u << (p & 31u), 0u));
             atomicOr(occ_at(c), bop3<TA & TB>(mok, 1u << (c & 31u), 0u));
             const uint32_t dxy = c ^ p;
-            if constexpr (UKEY) {
-              if constexpr (REV) {
-                uint32_t z;   // 1 for a stay: v_ffbl of 0 is ~0
-                asm("v_ffbl_b32 %0, %1" : "=v"(z) : "v"(dd));
-                sk[sidx] = bop3<~TA | (TB ^ TC)>(mok, kpr, z >> 31);
-              } else {
-                // No lane of the wave has co-located agents: a later agent can then never make the
-                // same move p -> c as an accepted one (it would have to stand on p too), so every
-                // stored key may carry the flipped low bit a stay's needs -- one op instead of three
-                sk[sidx] = bop3<~TA | (TB ^ TC)>(mok, kpr, 1u);
-              }
+            if constexpr (REV) {
+              uint32_t z;   // 1 for a stay: v_ffbl of 0 is ~0
+              asm("v_ffbl_b32 %0, %1" : "=v"(z) : "v"(dd));
+              sk[sidx] = bop3<~TA | (TB ^ TC)>(mok, kpr, z >> 31);
             } else {
-              if constexpr (REV) rk[sidx] = bop3<~TA | TB>(mok, (c & XY16) | ((p & XY16) << 8), 0u);
-              xk[sidx] = bop3<~TA | (TB ^ TC)>(mok, ukey, 0xFE000000u);
+              // No lane of the wave has co-located agents: a later agent can then never make the
+              // same move p -> c as an accepted one (it would have to stand on p too), so every
+              // stored key may carry the flipped low bit a stay's needs -- one op instead of three
+              sk[sidx] = bop3<~TA | (TB ^ TC)>(mok, kpr, 1u);
             }
             const uint32_t moved = bop3<TA ^ (TB & TC)>(a, mok, dxy);
             s.ag[sidx] = moved;
@@ -1337,13 +1197,11 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
             cp[sidx] = L.cell_row(moved);
             if (sidx >= PD) tb[sidx - PD] = *L.row_byte(cp[sidx >= PD ? sidx - PD : 0], tid);
             if (sidx >= 2 * PD) dst[sidx - 2 * PD] = L.dst_tb(tb[sidx >= 2 * PD ? sidx - 2 * PD : 0]);
-            if (PICK_IN_LOOP && !(ablate & 8) && sidx >= 3 * PD) {
+            if (!(ablate & 8) && sidx >= 3 * PD) {
               const int j = sidx >= 3 * PD ? sidx - 3 * PD : 0;
               pick(j, cp[j], tb[j], dst[j]);
             }
           }
-          // pin the hoisted block to this basic block (LLVM would sink it back to its only use)
-          if constexpr (HOIST) asm volatile("" : "+v"(rblk0.x), "+v"(rblk0.y), "+v"(rblk0.z), "+v"(rblk0.w));
         };
         // did an agent that shares a cell move?  (positions are final after the move loop: a pickup
         // changes target bytes only)
@@ -1357,20 +1215,16 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         // Where the reverse-key loop runs exactly for the waves with shared cells, that test is made
         // on its (rare) side of the branch, so the common path has no branch between the pickup
         // tail and regeneration item 0 and the two are scheduled as one block.
-#if defined(WH_FORCE_NOREV) || defined(WH_NO_PICK_MERGE)   // (A/B: the test after the pickup tail)
+#ifdef WH_NO_PICK_MERGE   // (A/B: the test after the pickup tail)
         constexpr bool CM_IN_REV = false;
 #else
         constexpr bool CM_IN_REV = LAZY && C::NAM <= kRevSplitMaxNam;
 #endif
-        // REV: the exact loop for waves with co-located agents (reverse keys in the two-key form; in
-        // the one-key form every stay's key flipped), else the loop for waves without any (no reverse
-        // keys / every key flipped).  From kRevSplitMaxNam agents on a single (exact) loop.
-#ifdef WH_FORCE_NOREV   // timing-only A/B builds: never the reverse-key loop (wrong with co-located agents)
-        if (!LAZY)
-#else
-        if (!LAZY || C::NAM > kRevSplitMaxNam || WH_RARE(__any(lg->cm != 0u)))
-#endif
-        {
+        // REV: the exact loop for waves with co-located agents (only a stay's key flipped), else the
+        // loop for waves without any (every key flipped).  The lazy grid knows the lanes with shared
+        // cells (lg->cm, from the last rebuild; new sharing needs an existing one).  From
+        // kRevSplitMaxNam agents on a single (exact) loop.
+        if (!LAZY || C::NAM > kRevSplitMaxNam || WH_RARE(__any(lg->cm != 0u))) {
 #ifdef WH_COUNT_REV   // A/B builds: count the wave-steps that take the reverse-key loop (wh_check_read)
           if (LAZY && __lane_id() == 0) atomicAdd(&g_wh_revcount[0], 1ull);
 #endif
@@ -1388,7 +1242,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         for (int i = (C::NAM > PD ? C::NAM - PD : 0); i < C::NAM; ++i) tb[i] = *L.row_byte(cp[i], tid);
 #pragma unroll
         for (int i = (C::NAM > 2 * PD ? C::NAM - 2 * PD : 0); i < C::NAM; ++i) dst[i] = L.dst_tb(tb[i]);
-        if (PICK_IN_LOOP && !(ablate & 8)) {
+        if (!(ablate & 8)) {
 #pragma unroll
           for (int i = (C::NAM > 3 * PD ? C::NAM - 3 * PD : 0); i < C::NAM; ++i) pick(i, cp[i], tb[i], dst[i]);
         }
@@ -1410,8 +1264,6 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         for (int i = 0; i < C::NAM; ++i) tb[i] = *L.row_byte(cp[i], tid);
 #pragma unroll
         for (int i = 0; i < C::NAM; ++i) dst[i] = L.dst_tb(tb[i]);
-      }
-      if (!looked || !PICK_IN_LOOP) {
 #pragma unroll
         for (int i = 0; i < C::NAM; ++i) pick(i, cp[i], tb[i], dst[i]);
       }
@@ -1439,7 +1291,9 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
       uint32_t rlo = (uint32_t)inactive, rhi = (uint32_t)(inactive >> 32);   // still selectable
       uint32_t ulo = 0, uhi = 0;                                               // targets used
       uint32_t olo = 0, ohi = 0;                                               // points opened
-      uint32_t tj[3] = {0u, 0u, 0u};   // targets of items 0-2 (kRegenSkip)
+      // Targets of items 1 and 2 by skipping the earlier items' targets (a compare-add each) instead
+      // of a rank selection on a used-target mask; the mask is built only from item 3 on.  Same values.
+      uint32_t tj[3] = {0u, 0u, 0u};   // targets of items 0-2
       uint32_t first_t = 0;
       const uint32_t wexp = ((t + W) & 0xFFu) << 8;   // expires at step t + W
       uint4 blk = make_uint4(0u, 0u, 0u, 0u);   // words 2j (pickup) and 2j+1 (target) share a block
@@ -1458,20 +1312,20 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
             ma = bop3<TA & TB>(ma, 0u - (uint32_t)valid, 0u);
             sel = select_bit64(inactive, rpos);   // positions into the inactive list, host-drawn
           } else {
-            if ((j & 1) == 0) blk = ((HOIST || kHoistPolicy) && j == 0 && hoisted) ? rblk0 : stream_block(k, gid, s.epi, t, PUR_REGEN, (uint32_t)(j >> 1));
+            if ((j & 1) == 0) blk = (j == 0 && pre_rblk) ? rblk0 : stream_block(k, gid, s.epi, t, PUR_REGEN, (uint32_t)(j >> 1));
             const uint32_t w1 = comp(blk, (2 * j) & 3), w2 = comp(blk, (2 * j + 1) & 3);
             sel = select_bit64(((uint64_t)rhi << 32) | rlo, __umulhi(w1, nin - (uint32_t)j));
             const uint32_t r2 = __umulhi(w2, (uint32_t)(C::DP - j));
             if (j == 0) tgi = r2;                                               // nothing used yet
             else if (j == 1) tgi = r2 + ((first_t - 1u - r2) >> 31);   // + (r2 >= first): skip it
-            else if (kRegenSkip && j == 2) {
+            else if (j == 2) {
               // the r2-th target not used by items 0 and 1: skip each of them at or below it, in
               // ascending order (the same value as the rank selection on the used mask)
               const uint32_t lo = min(tj[0], tj[1]), hi = max(tj[0], tj[1]);
               tgi = r2 + ((lo - 1u - r2) >> 31);
               tgi += (hi - 1u - tgi) >> 31;
             } else {
-              if (kRegenSkip && j == 3) {   // from item 3 on: the used mask, built from items 0-2
+              if (j == 3) {   // from item 3 on: the used mask, built from items 0-2
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                   const uint64_t b = 1ull << (tj[q] & 63u);
@@ -1490,7 +1344,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
           rhi &= ~shi;
           olo |= slo;
           ohi |= shi;
-          if (!kRegenSkip || j >= 3) {   // (kRegenSkip: items 0-2 skip their targets arithmetically)
+          if (j >= 3) {   // (items 0-2 skip their targets arithmetically)
             ulo = bop3<(TA & TB) | TC>(ma, (uint32_t)tb64, ulo);
             uhi = bop3<(TA & TB) | TC>(ma, (uint32_t)(tb64 >> 32), uhi);
           }
@@ -1792,12 +1646,8 @@ __device__ __forceinline__ void run_steps(const StepParams& a, Regs<C>& s, Lds<C
 // auto-reset on, no returns / episode stats / env mask, na == NAM with NAM even (16/8-byte reward
 // rows).  No per-step tests of launch options, and the injected-draw path is compiled out, so a
 // step executes few branch instructions -- each costs several issue slots at one wave per SIMD
-// (tools/oprate5.hip: ~8 ns per s_cbranch/s_branch against ~2.6 ns per VALU op).
-#ifndef WH_EAGER_GRID   // (A/B builds: -DWH_EAGER_GRID rebuilds the grid every step)
-constexpr bool kLazyGrid = true;
-#else
-constexpr bool kLazyGrid = false;
-#endif
+// (tools/oprate5.hip: ~8 ns per s_cbranch/s_branch against ~2.6 ns per VALU op).  Its steps keep the
+// grid between them (step_env's LAZY form).
 
 // Lanes of a wave ending their episodes in the same step that are reset one at a time from their
 // reset slots (~40 issue slots each); more than this take the all-lane reset_philox (~700 VALU).
@@ -1871,7 +1721,7 @@ struct FastRun {
       policy_steps<C, POLICY, POLICY == POL_GREEDY && !kAblationBuild>(s, L, k, gid, a.p, d);
     }
     float rew[C::NAM];
-    const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, kLazyGrid>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
+    const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, true>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
                                                 (uint32_t)a.T, (uint32_t)a.W, rew, nullptr, tid, ablate, &lg);
     if (!(ablate & 64)) {
       store_row<C>(rrow, rew);
@@ -1884,7 +1734,6 @@ struct FastRun {
       // a few envs of a full wave end (desynchronised episodes): wave-wide resets of them, one env
       // at a time (every lane takes part, so not in a tail wave whose lanes past B have exited)
       const bool full = __ballot(true) == ~0ull;
-#ifndef WH_NO_RESET_SLOTS   // (A/B builds: -DWH_NO_RESET_SLOTS resets one lane from scratch)
       if (SLOTS && a.steps >= kSlotMinSteps && __popcll(dm) <= kSlotResetMax && full) {
         // their precomputed next-episode states, after (re)filling the wave's slots if one of
         // theirs is stale: one wave-wide fill (every lane's next episode) serves the resets of
@@ -1895,9 +1744,7 @@ struct FastRun {
           for (uint64_t m = dm; m; m &= m - 1ull) reset_from_slot<C, C::NAM>(s, L, *RS, (uint32_t)a.W, tid, __builtin_ctzll(m));
           lg.rebuild = lg.rebuild || done;   // their grid columns were cleared
         }
-      } else
-#endif
-      if (__popcll(dm) == 1 && full) {
+      } else if (__popcll(dm) == 1 && full) {
         // short launches (the sampler's 1-step ones): a fill would serve few later resets
         reset_lane<C, C::NAM>(s, L, k, gid, a.variable_n, (uint32_t)a.W, tid, __builtin_ctzll(dm));
         lg.rebuild = lg.rebuild || done;   // its grid column was cleared
@@ -1952,15 +1799,16 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
     } else {
       policy_steps<C, POLICY, POLICY == POL_GREEDY && !kAblationBuild>(s, L, k, gid, a.p, d);
     }
-    uint4 rb = make_uint4(0u, 0u, 0u, 0u);
-    if constexpr (kHoistPolicy) {   // pinned to the policy's block (LLVM would sink it to its use)
-      rb = stream_block(k, gid, s.epi, (s.hdr + 1u) & 0xFFFFu, PUR_REGEN, 0u);
-      asm volatile("" : "+v"(rb.x), "+v"(rb.y), "+v"(rb.z), "+v"(rb.w));
-    }
+    // The regeneration almost always draws (some lane of the wave reopens a point on nearly every
+    // step), so its first Philox block -- a chain of ten dependent rounds -- is computed here, where
+    // it fills the policy block's issue gaps: -0.5 % per step at Medium-8 and Large-16 against the
+    // move loop's block (profiles/r05_step3_ab.txt).  Pinned: LLVM would sink it to its use.
+    uint4 rb = stream_block(k, gid, s.epi, (s.hdr + 1u) & 0xFFFFu, PUR_REGEN, 0u);
+    asm volatile("" : "+v"(rb.x), "+v"(rb.y), "+v"(rb.z), "+v"(rb.w));
     float rew[C::NAM];
-    const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, kLazyGrid>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
+    const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, true>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
                                                 (uint32_t)a.T, (uint32_t)a.W, rew, nullptr, tid, ablate, &lg,
-                                                kHoistPolicy ? &rb : nullptr);
+                                                &rb);
     if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);   // the next step's (redone below after a reset)
     if (!(ablate & 64)) {
       store_row<C>(rrow + tid * C::NAM, rew);
@@ -1973,7 +1821,6 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
       // a few envs of a full wave end (desynchronised episodes): wave-wide resets of them, one env
       // at a time (every lane takes part, so not in a tail wave whose lanes past B have exited)
       const bool full = __ballot(true) == ~0ull;
-#ifndef WH_NO_RESET_SLOTS   // (A/B builds: -DWH_NO_RESET_SLOTS resets one lane from scratch)
       if (SLOTS && a.steps >= kSlotMinSteps && __popcll(dm) <= kSlotResetMax && full) {
         // their precomputed next-episode states, after (re)filling the wave's slots if one of
         // theirs is stale: one wave-wide fill (every lane's next episode) serves the resets of
@@ -1984,9 +1831,7 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
           for (uint64_t m = dm; m; m &= m - 1ull) reset_from_slot<C, C::NAM>(s, L, *RS, (uint32_t)a.W, tid, __builtin_ctzll(m));
           lg.rebuild = lg.rebuild || done;   // their grid columns were cleared
         }
-      } else
-#endif
-      if (__popcll(dm) == 1 && full) {
+      } else if (__popcll(dm) == 1 && full) {
         // short launches (the sampler's 1-step ones): a fill would serve few later resets
         reset_lane<C, C::NAM>(s, L, k, gid, a.variable_n, (uint32_t)a.W, tid, __builtin_ctzll(dm));
         lg.rebuild = lg.rebuild || done;   // its grid column was cleared
@@ -2246,8 +2091,7 @@ __device__ __forceinline__ void stream_frags(const uint32_t* lims, const uint32_
     }
     typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
     const u32x4v v = {w[0], w[1], w[2], w[3]};
-    if constexpr (kFragNT) __builtin_nontemporal_store(v, reinterpret_cast<u32x4v*>(&out[c]));
-    else *reinterpret_cast<u32x4v*>(&out[c]) = v;
+    *reinterpret_cast<u32x4v*>(&out[c]) = v;   // plain: the policy network reads it next (see rows_nt)
   }
 }
 

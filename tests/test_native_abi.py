@@ -71,7 +71,7 @@ def test_variant_build_fails_provenance(tmp_path):
     plain = _probe_version(tmp_path / "plain")
     assert _native.parse_version(plain) == (sha, "")
     _native.check_provenance(plain, sha)
-    for k, args in enumerate((["EXTRA=-DWH_ABLATION"], ["EXTRA=-DWH_FORCE_NOREV"], ["SCHED_warehouse_amd=-mllvm -amdgpu-sched-strategy=max-ilp"],
+    for k, args in enumerate((["EXTRA=-DWH_ABLATION"], ["EXTRA=-DWH_TIMING"], ["SCHED_warehouse_amd=-mllvm -amdgpu-sched-strategy=max-ilp"],
                  ["FLAGS=--offload-arch=gfx950 -O1"])):
         v = _probe_version(tmp_path / f"v{k}", *args)   # (a distinct path each: dlopen caches by path)
         got_sha, variant = _native.parse_version(v)
