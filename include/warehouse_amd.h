@@ -35,7 +35,7 @@
  * from the PHILOX contract: Philox4x32-10 keyed by `seed`, counter (env_offset + e, episode, t,
  * purpose << 24 | block); purposes RESET=1, REGEN=2, POLICY=3, RANDOM=4 (word layout in
  * DESIGN.md §RNG and oracle/philox.py; 5 = the policy network's sampling noise, 6 = replay index
- * draws, with the counters their entry points state).  Philox trajectories depend only on the global env id,
+ * draws, 7 = prioritized replay masses, with the counters their entry points state).  Philox trajectories depend only on the global env id,
  * so any sharding of env ids over GPUs reproduces them exactly.
  */
 #ifndef WAREHOUSE_AMD_H
@@ -371,6 +371,67 @@ typedef struct wh_replay_batch {
  * returns WH_ENOTSUP when a fragment output is requested. */
 int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t filled, int64_t M,
                      const int64_t* idx, uint64_t seed, uint64_t draw, const wh_replay_batch* batch, void* stream);
+
+/* REPLAY PRIORITIES: a sum tree over the ring's entries for prioritized sampling, in integer
+ * arithmetic only, so both engines (and a numpy model) agree bit for bit and no result depends on
+ * the order atomics arrive in.  The layout is the same for both engines: a tree moves between them
+ * with a plain copy, like the ring.
+ *   Index space  leaf i is ring entry i = slot * B + env (the index wh_replay_gather takes);
+ *                count = capacity * B leaves, 1 <= count <= 2^31.
+ *   Leaves       uint32 fixed-point priorities q, WH_PRIO_ONE = priority 1.0.  A stored q lies in
+ *                [1, 2^31 - 1]; 0 = no transition here, never sampled.
+ *   Quantising   a priority p (f32, already raised to alpha), x = p * 1048576.0f:
+ *                NaN or !(x >= 1) -> q = 1;  x >= 2147483648 -> q = 0x7FFFFFFF;  else q = (uint32_t)x
+ *                (the same in every denormal mode: whatever a flush could change is below 1).
+ *   Shape        radix 16.  Level 0 is the leaves, padded with zeros to a multiple of 16; level
+ *                k >= 1 has n_k = ceil(n_{k-1} / 16) uint64 sums (entry j = the sum of entries
+ *                16 j .. 16 j + 15 of level k - 1), padded with zeros to a multiple of 16.  `node`
+ *                holds levels 1, 2, ... one after the other; the level with n_k == 1 is the root,
+ *                the total (count <= 16: one level above the leaves).  The 16 children of an
+ *                entry are 128 bytes, one cache line.  Sums stay below 2^62, so signed deltas
+ *                applied as wrapping 64-bit adds are exact.
+ * An all-zero tree with *max_q = WH_PRIO_ONE is the empty tree.  The buffers are the caller's, of
+ * the sizes wh_replay_prio_query states. */
+#define WH_PRIO_ONE (1u << 20)
+#define WH_PRIO_MAX 0x7FFFFFFFu
+#define WH_PRIO_MAX_COUNT ((int64_t)1 << 31)
+
+typedef struct wh_replay_prio {
+  uint32_t* leaf;    /* [leaf_words] */
+  uint64_t* node;    /* [node_words]  levels 1 .. levels, bottom-up */
+  uint32_t* max_q;   /* [1]  the largest q an update has written (a fresh entry's priority) */
+  int64_t   count;   /* leaves: capacity * B */
+} wh_replay_prio;
+
+/* Sizes of a tree of `count` leaves: leaf_words uint32, node_words uint64, `levels` levels above
+ * the leaves (any output may be NULL).  WH_EINVAL unless 1 <= count <= 2^31. */
+int wh_replay_prio_query(int64_t count, int64_t* leaf_words, int64_t* node_words, int32_t* levels);
+
+/* Set leaves [first, first + n) and update their ancestors, one launch:
+ *   mode 0  every leaf becomes q (0 <= q <= 2^31 - 1; q = 0 clears the range)
+ *   mode 1  every leaf becomes the tree's current *max_q, read on the device (no host sync): what a
+ *           recorder does with a fresh slot (RLlib gives new items the maximum priority); q ignored
+ * *max_q is left as it is.  n = 0 launches nothing. */
+int wh_replay_prio_fill(const wh_replay_prio* tree, int64_t first, int64_t n, int32_t mode, uint32_t q,
+                        void* stream);
+
+/* Leaf idx[m] <- quantise(p[m]) for m < M (idx [M] int64, p [M] f32), ancestors updated, *max_q <-
+ * the maximum of itself and every q written.  An index outside [0, count) is ignored.  Duplicate
+ * indices: the largest q wins, so the result does not depend on execution order.  Two launches on
+ * `stream` (clear the touched leaves; raise them to their q).  M = 0 launches nothing. */
+int wh_replay_prio_update(const wh_replay_prio* tree, int64_t M, const int64_t* idx, const float* p,
+                          void* stream);
+
+/* Draw M leaves with probability q / total, one launch.  Sample m takes r = u[m] (u [M] uint64,
+ * injected draws) or, u = NULL, r = w0 << 32 | w1 of the philox contract, purpose 7: counter
+ * (m, draw & 0xFFFFFFFF, draw >> 32, 7 << 24) keyed by seed.  mass = (r * total) >> 64; the descent
+ * takes in every node the first child whose inclusive prefix sum exceeds the mass left, and
+ * subtracts that child's exclusive prefix.  idx_out [M] int64: the leaf reached; q_out [M] (or
+ * NULL): its q; total_out [1] (or NULL): the root as this launch read it, so weights can be
+ * computed later without racing an update.  An empty tree (total == 0) gives idx_out = -1 and
+ * q_out = 0, which wh_replay_gather turns into n = -1 and a zero sample.  M = 0 launches nothing. */
+int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t* u, uint64_t seed, uint64_t draw,
+                          int64_t* idx_out, uint32_t* q_out, uint64_t* total_out, void* stream);
 
 /* Library build identification (e.g. "warehouse_amd gfx950 <date>"). */
 const char* wh_version(void);

@@ -255,4 +255,74 @@ inline int replay_gather_call(Shape* g, const wh_config* cfg, int64_t B, const w
   return B < 0 ? WH_EINVAL : WH_OK;
 }
 
+// ----------------------------------------------------------------------------- replay priorities
+// The radix-16 tree of `count` leaves (include/warehouse_amd.h, REPLAY PRIORITIES): level k >= 1
+// has n[k] sums and starts at word off[k] of `node`; level `levels` is the root.
+constexpr int PRIO_MAX_LEVELS = 8;   // 2^31 leaves: 2^27, 2^23, ... 2^3, 1 sums
+
+struct PrioShape {
+  int32_t levels;
+  int64_t leaf_words, node_words;
+  int64_t n[PRIO_MAX_LEVELS + 1], off[PRIO_MAX_LEVELS + 1];   // [0]: the leaves (off unused)
+};
+
+inline int64_t pad16(int64_t n) { return (n + 15) & ~(int64_t)15; }
+
+inline int prio_shape(int64_t count, PrioShape* s) {
+  if (count < 1 || count > WH_PRIO_MAX_COUNT) return WH_EINVAL;
+  *s = PrioShape{};
+  s->n[0] = count;
+  s->leaf_words = pad16(count);
+  int64_t n = count;
+  do {
+    n = (n + 15) / 16;
+    ++s->levels;
+    s->n[s->levels] = n;
+    s->off[s->levels] = s->node_words;
+    s->node_words += pad16(n);
+  } while (n > 1);
+  return WH_OK;
+}
+
+// Required pointers, then the sizes, then M < 0; the pointers of the batch only for M > 0.
+inline int prio_tree(const wh_replay_prio* t, PrioShape* s) {
+  if (!t || !t->leaf || !t->node || !t->max_q) return WH_EINVAL;
+  return prio_shape(t->count, s);
+}
+
+// wh_replay_prio_fill
+inline int prio_fill_call(PrioShape* s, const wh_replay_prio* t, int64_t first, int64_t n, int32_t mode, uint32_t q) {
+  if ((mode != 0 && mode != 1) || (mode == 0 && q > WH_PRIO_MAX)) return WH_EINVAL;
+  const int rc = prio_tree(t, s);
+  if (rc) return rc;
+  return (first < 0 || n < 0 || first > t->count || n > t->count - first) ? WH_EINVAL : WH_OK;
+}
+
+// wh_replay_prio_update
+inline int prio_update_call(PrioShape* s, const wh_replay_prio* t, int64_t M, const int64_t* idx, const float* p) {
+  if (M > 0 && (!idx || !p)) return WH_EINVAL;
+  const int rc = prio_tree(t, s);
+  if (rc) return rc;
+  return M < 0 ? WH_EINVAL : WH_OK;
+}
+
+// wh_replay_prio_sample
+inline int prio_sample_call(PrioShape* s, const wh_replay_prio* t, int64_t M, const int64_t* idx_out) {
+  if (M > 0 && !idx_out) return WH_EINVAL;
+  const int rc = prio_tree(t, s);
+  if (rc) return rc;
+  return M < 0 ? WH_EINVAL : WH_OK;
+}
+
+// the quantisation rule, one for both engines (plain C++: also device code)
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline uint32_t prio_quantise(float p) {
+  const float x = p * 1048576.0f;
+  if (!(x >= 1.0f)) return 1u;   // (a NaN fails the comparison)
+  if (x >= 2147483648.0f) return WH_PRIO_MAX;
+  return (uint32_t)x;
+}
+
 }  // namespace wh_abi

@@ -846,6 +846,98 @@ int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring
   return WH_OK;
 }
 
+// ---- replay priorities (include/warehouse_amd.h, REPLAY PRIORITIES): the device's layout and
+// rules in plain serial loops -- integer sums, so the tree is the device's bit for bit
+static void prio_add(const wh_replay_prio* t, const wh_abi::PrioShape& s, int64_t leaf, uint64_t delta) {
+  for (int k = 1; k <= s.levels; ++k) t->node[s.off[k] + (leaf >> (4 * k))] += delta;   // (wrapping: a signed delta)
+}
+
+int wh_replay_prio_query(int64_t count, int64_t* leaf_words, int64_t* node_words, int32_t* levels) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_shape(count, &s);
+  if (rc) return rc;
+  if (leaf_words) *leaf_words = s.leaf_words;
+  if (node_words) *node_words = s.node_words;
+  if (levels) *levels = s.levels;
+  return WH_OK;
+}
+
+int wh_replay_prio_fill(const wh_replay_prio* tree, int64_t first, int64_t n, int32_t mode, uint32_t q, void*) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_fill_call(&s, tree, first, n, mode, q);
+  if (rc || n == 0) return rc;
+  if (mode) q = *tree->max_q;
+  for (int64_t i = first; i < first + n; ++i) {
+    const uint64_t delta = (uint64_t)q - (uint64_t)tree->leaf[i];
+    tree->leaf[i] = q;
+    if (delta) prio_add(tree, s, i, delta);
+  }
+  return WH_OK;
+}
+
+int wh_replay_prio_update(const wh_replay_prio* tree, int64_t M, const int64_t* idx, const float* p, void*) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_update_call(&s, tree, M, idx, p);
+  if (rc || M == 0) return rc;
+  // clear every touched leaf, then raise it to the largest q given for it
+  for (int64_t m = 0; m < M; ++m) {
+    const int64_t i = idx[m];
+    if (i < 0 || i >= tree->count || !tree->leaf[i]) continue;
+    prio_add(tree, s, i, 0ull - (uint64_t)tree->leaf[i]);
+    tree->leaf[i] = 0;
+  }
+  uint32_t qmax = *tree->max_q;
+  for (int64_t m = 0; m < M; ++m) {
+    const int64_t i = idx[m];
+    if (i < 0 || i >= tree->count) continue;
+    const uint32_t q = wh_abi::prio_quantise(p[m]);
+    qmax = std::max(qmax, q);
+    if (q <= tree->leaf[i]) continue;
+    prio_add(tree, s, i, (uint64_t)(q - tree->leaf[i]));
+    tree->leaf[i] = q;
+  }
+  *tree->max_q = qmax;
+  return WH_OK;
+}
+
+int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t* u, uint64_t seed, uint64_t draw,
+                          int64_t* idx_out, uint32_t* q_out, uint64_t* total_out, void*) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_sample_call(&s, tree, M, idx_out);
+  if (rc || M == 0) return rc;
+  const uint32_t k0 = keys_lo(seed), k1 = keys_hi(seed);
+  const uint64_t total = tree->node[s.off[s.levels]];
+  if (total_out) *total_out = total;
+  for (int64_t m = 0; m < M; ++m) {
+    uint64_t r;
+    if (u) {
+      r = u[m];
+    } else {
+      const U4 w = philox10((uint32_t)m, (uint32_t)(draw & 0xFFFFFFFFu), (uint32_t)(draw >> 32), 7u << 24, k0, k1);
+      r = (uint64_t)w.v[0] << 32 | w.v[1];
+    }
+    uint64_t mass = (uint64_t)(((unsigned __int128)r * total) >> 64);
+    int64_t pos = 0;
+    uint32_t q = 0;
+    for (int k = s.levels - 1; k >= 0; --k) {
+      // the first child whose inclusive prefix exceeds the mass (none: the last, as the device does)
+      uint64_t ex = 0;
+      int j = 0;
+      for (;; ++j) {
+        const uint64_t v = k ? tree->node[s.off[k] + pos * 16 + j] : (uint64_t)tree->leaf[pos * 16 + j];
+        q = (uint32_t)v;
+        if (ex + v > mass || j == 15) break;
+        ex += v;
+      }
+      mass -= ex;
+      pos = std::min(pos * 16 + j, s.n[k] - 1);
+    }
+    idx_out[m] = total ? pos : -1;
+    if (q_out) q_out[m] = total ? q : 0u;
+  }
+  return WH_OK;
+}
+
 // ---- what the CPU has no use for: the policy network and its fragment operand (device formats),
 // the two-stream sampler step, prepared launches, assert-mode counters, and the 16-lanes-per-env
 // form (csrc/step_wide.h: the host engine has no lanes)

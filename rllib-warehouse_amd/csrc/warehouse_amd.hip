@@ -2317,6 +2317,7 @@ __global__ __launch_bounds__(BT) void k_observe(const uint32_t* __restrict__ sta
 }
 
 #include "replay.h"
+#include "prio.h"
 
 // ----------------------------------------------------------------------------- fused sampler step
 // The sampler route (wh_sampler_step: device policy + step + auto-reset, then the observation rows)
@@ -3421,6 +3422,67 @@ int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring
   a.idx_out = batch->idx_out;
   hipLaunchKernelGGL(k->replay_gather[sel], dim3((unsigned)(groups * (next ? 2 : 1))), dim3(BT), 0,
                      (hipStream_t)stream, a);
+  return hip_err(hipGetLastError());
+}
+
+// ---- replay priorities (csrc/prio.h).  abi_args.h has checked the call.
+static PrioTree prio_tree_of(const wh_replay_prio* tree, const wh_abi::PrioShape& s) {
+  PrioTree t{};
+  t.leaf = tree->leaf;
+  t.node = tree->node;
+  t.max_q = tree->max_q;
+  t.count = tree->count;
+  t.levels = s.levels;
+  for (int k = 0; k <= s.levels; ++k) {
+    t.n[k] = s.n[k];
+    t.off[k] = s.off[k];
+  }
+  return t;
+}
+
+int wh_replay_prio_query(int64_t count, int64_t* leaf_words, int64_t* node_words, int32_t* levels) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_shape(count, &s);
+  if (rc) return rc;
+  if (leaf_words) *leaf_words = s.leaf_words;
+  if (node_words) *node_words = s.node_words;
+  if (levels) *levels = s.levels;
+  return WH_OK;
+}
+
+int wh_replay_prio_fill(const wh_replay_prio* tree, int64_t first, int64_t n, int32_t mode, uint32_t q,
+                        void* stream) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_fill_call(&s, tree, first, n, mode, q);
+  if (rc || n == 0) return rc;
+  PrioFillParams a{prio_tree_of(tree, s), first, first + n, first & ~(int64_t)(BT - 1), mode, q};
+  hipLaunchKernelGGL(k_prio_fill, grid_for(a.end - a.base), dim3(BT), 0, (hipStream_t)stream, a);
+  return hip_err(hipGetLastError());
+}
+
+int wh_replay_prio_update(const wh_replay_prio* tree, int64_t M, const int64_t* idx, const float* p,
+                          void* stream) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_update_call(&s, tree, M, idx, p);
+  if (rc || M == 0) return rc;
+  if ((M + BT - 1) / BT > 0x7FFFFFFF) return WH_EINVAL;
+  PrioUpdateParams a{prio_tree_of(tree, s), M, idx, p, 0};
+  hipLaunchKernelGGL(k_prio_update, grid_for(M), dim3(BT), 0, (hipStream_t)stream, a);
+  a.phase = 1;
+  hipLaunchKernelGGL(k_prio_update, grid_for(M), dim3(BT), 0, (hipStream_t)stream, a);
+  return hip_err(hipGetLastError());
+}
+
+int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t* u, uint64_t seed, uint64_t draw,
+                          int64_t* idx_out, uint32_t* q_out, uint64_t* total_out, void* stream) {
+  wh_abi::PrioShape s;
+  const int rc = wh_abi::prio_sample_call(&s, tree, M, idx_out);
+  if (rc || M == 0) return rc;
+  const int64_t groups = (M + BT / 16 - 1) / (BT / 16);
+  if (groups > 0x7FFFFFFF) return WH_EINVAL;
+  PrioSampleParams a{prio_tree_of(tree, s), M, u, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
+                     (uint32_t)(draw & 0xFFFFFFFFu), (uint32_t)(draw >> 32), idx_out, q_out, total_out};
+  hipLaunchKernelGGL(k_prio_sample, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, a);
   return hip_err(hipGetLastError());
 }
 

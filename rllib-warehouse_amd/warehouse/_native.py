@@ -45,7 +45,12 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_check_read", "wh_rollout_prepare", "wh_launch_run", "wh_launch_run_timed", "wh_launch_free",
            "wh_sampler_step", "wh_sampler_step_to", "wh_sampler_rollout", "wh_vector_step_x",
            "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide",
-           "wh_replay_put", "wh_replay_gather")
+           "wh_replay_put", "wh_replay_gather",
+           "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample")
+
+WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
+WH_PRIO_MAX = 0x7FFFFFFF       # the largest stored priority
+WH_PRIO_MAX_COUNT = 1 << 31    # leaves of the largest tree
 
 
 class WhConfig(ctypes.Structure):
@@ -98,6 +103,11 @@ class WhReplayBatch(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in
                 ("obs", "next_obs", "xfrag", "next_xfrag", "state", "next_state", "actions", "rewards", "dones",
                  "n", "idx_out")]
+
+
+class WhReplayPrio(ctypes.Structure):
+    _fields_ = [("leaf", ctypes.c_void_p), ("node", ctypes.c_void_p), ("max_q", ctypes.c_void_p),
+                ("count", ctypes.c_int64)]
 
 
 WH_MLP_BF16 = 0
@@ -186,6 +196,11 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_replay_put.argtypes = [_CFG, _I64, ctypes.POINTER(WhReplayRing), _I64, _I32, _P, _P, _P, _P, _P]
     S.wh_replay_gather.argtypes = [_CFG, _I64, ctypes.POINTER(WhReplayRing), _I64, _I64, _P, _U64, _U64,
                                    ctypes.POINTER(WhReplayBatch), _P]
+    _PT = ctypes.POINTER(WhReplayPrio)
+    S.wh_replay_prio_query.argtypes = [_I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]
+    S.wh_replay_prio_fill.argtypes = [_PT, _I64, _I64, _I32, ctypes.c_uint32, _P]
+    S.wh_replay_prio_update.argtypes = [_PT, _I64, _P, _P, _P]
+    S.wh_replay_prio_sample.argtypes = [_PT, _I64, _P, _U64, _U64, _P, _P, _P, _P]
     _MD = ctypes.POINTER(WhMlpDesc)
     S.wh_mlp_query.argtypes = [_MD, ctypes.POINTER(ctypes.c_int64)]
     S.wh_mlp_pack.argtypes = [_MD] + [_P] * 7

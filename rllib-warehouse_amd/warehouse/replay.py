@@ -12,6 +12,16 @@ packed states, in one launch.
     obs, rew, done = buf.step(actions)           # a recorded vector_step(autoreset=True)
     batch = buf.sample(64)                       # obs, next_obs, actions, rewards, dones, n, idx_out
 
+With `prioritized=True` the buffer also keeps a priority tree over its entries (include/
+warehouse_amd.h, REPLAY PRIORITIES; csrc/prio.h): a recorded slot enters at the largest priority seen
+so far, `sample()` draws entries in proportion to their priority and returns importance weights,
+and `update_priorities()` writes the learner's new ones.  All of it is integer arithmetic on the
+device (or the host engine), exact and the same on both, with no host sync.
+
+    buf = ReplayBuffer(env, capacity=200, prioritized=True)
+    batch = buf.sample(64, beta=0.4)             # ... plus prio_q, weights
+    buf.update_priorities(batch["idx_out"], td_error)
+
 `dones` is what the step reported; a learner that follows the reference's `no_done_at_end: true`
 ignores it at the bootstrap, and `next_obs` of such a sample is the terminal observation (not the
 first one of the next episode).
@@ -34,7 +44,10 @@ class ReplayBuffer:
     """A ring of `capacity` time steps of every env of `env` (slot = one step of all B envs), on
     the env's device with the env's engine (device="cpu": the host engine, no fragments)."""
 
-    def __init__(self, env: BatchedWarehouse, capacity: int):
+    def __init__(self, env: BatchedWarehouse, capacity: int, prioritized: bool = False, alpha: float = 0.6,
+                 eps: float = 1e-6):
+        """`prioritized`: keep a priority tree (RLlib's `prioritized_replay`), with RLlib's
+        `prioritized_replay_alpha` and `prioritized_replay_eps` as `alpha` and `eps`."""
         capacity = int(capacity)
         if capacity < 1:
             raise ValueError(f"capacity: at least 1 slot, got {capacity}")
@@ -51,6 +64,32 @@ class ReplayBuffer:
         self._filled = 0
         self._draw = 0
         self._out: Dict[tuple, torch.Tensor] = {}
+        self.prioritized = bool(prioritized)
+        if self.prioritized:
+            self._init_tree(float(alpha), float(eps))
+
+    def _init_tree(self, alpha: float, eps: float) -> None:
+        """The empty tree: all-zero leaves and sums, max_q = priority 1.0.  Leaves and max_q are
+        int32 and the sums int64 tensors: a stored q is below 2^31 and a sum below 2^62, so the
+        signed views hold the same numbers."""
+        e = self.env
+        count = self.capacity * e.B
+        if not (alpha >= 0.0 and eps >= 0.0):
+            raise ValueError(f"alpha and eps: not negative, got {alpha}, {eps}")
+        lw, nw, lv = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int32()
+        nat.check(e._lib.wh_replay_prio_query(count, ctypes.byref(lw), ctypes.byref(nw), ctypes.byref(lv)),
+                  "wh_replay_prio_query")
+        self.alpha, self.eps = alpha, eps
+        self.prio_levels = lv.value
+        self.prio_leaf = torch.zeros(lw.value, dtype=torch.int32, device=e.device)
+        self.prio_node = torch.zeros(nw.value, dtype=torch.int64, device=e.device)
+        self.prio_max_q = torch.full((1,), nat.WH_PRIO_ONE, dtype=torch.int32, device=e.device)
+        self.prio_total = torch.zeros(1, dtype=torch.int64, device=e.device)
+        self._tree = nat.WhReplayPrio(self.prio_leaf.data_ptr(), self.prio_node.data_ptr(),
+                                      self.prio_max_q.data_ptr(), count)
+
+    def _prio_call(self, name, *args) -> None:
+        nat.check(getattr(self.env._lib, name)(ctypes.byref(self._tree), *args), name)
 
     # ------------------------------------------------------------------ recording
     @property
@@ -87,7 +126,10 @@ class ReplayBuffer:
         self._put(slot, 1)
 
     def advance(self) -> None:
-        """Count the slot at the cursor as filled and move on (step() does this itself)."""
+        """Count the slot at the cursor as filled and move on (step() does this itself).  A
+        prioritized buffer gives the slot's entries the largest priority seen so far."""
+        if self.prioritized:
+            self._prio_call("wh_replay_prio_fill", self._cursor * self.env.B, self.env.B, 1, 0, self.env.stream)
         self._cursor = (self._cursor + 1) % self.capacity
         self._filled = min(self._filled + 1, self.capacity)
 
@@ -104,6 +146,23 @@ class ReplayBuffer:
         self.advance()
         return obs, e.rewards, e.dones
 
+    def update_priorities(self, idx, priorities) -> None:
+        """Entry idx[m] (slot * B + env, what sample() returned as idx_out) gets the priority
+        (|priorities[m]| + eps) ** alpha, computed in f32 and quantised by the tree's rule.  An index
+        outside the ring is ignored; of duplicate indices the largest priority wins."""
+        if not self.prioritized:
+            raise ValueError("update_priorities: the buffer was made with prioritized=False")
+        e = self.env
+        ix = torch.as_tensor(np.asarray(idx) if not torch.is_tensor(idx) else idx)
+        ix = ix.to(device=e.device, dtype=torch.int64).contiguous()
+        pr = torch.as_tensor(np.asarray(priorities) if not torch.is_tensor(priorities) else priorities)
+        pr = pr.to(device=e.device, dtype=torch.float32)
+        if ix.dim() != 1 or pr.shape != ix.shape:
+            raise ValueError(f"idx and priorities: two [M] vectors, got {tuple(ix.shape)} and {tuple(pr.shape)}")
+        p = ((pr.abs() + self.eps) ** self.alpha).contiguous()
+        if ix.numel():
+            self._prio_call("wh_replay_prio_update", ix.numel(), ix.data_ptr(), p.data_ptr(), e.stream)
+
     # ------------------------------------------------------------------ sampling
     def _shapes(self, M: int):
         e = self.env
@@ -115,8 +174,15 @@ class ReplayBuffer:
                     actions=((M, NA), torch.int32), rewards=((M, NA), torch.float32), dones=((M,), torch.uint8),
                     n=((M,), torch.int32), idx_out=((M,), torch.int64))
 
+    def _own(self, k: str, M: int, shape, dt) -> torch.Tensor:
+        if (k, M) not in self._out:
+            self._out = {kk: v for kk, v in self._out.items() if kk[0] != k}   # one size kept per key
+            self._out[(k, M)] = torch.empty(shape, dtype=dt, device=self.env.device)
+        return self._out[(k, M)]
+
     def sample(self, M: int, idx=None, draw: Optional[int] = None, *, rows: bool = True, fragments: bool = False,
-               states: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+               states: bool = False, out: Optional[Dict[str, torch.Tensor]] = None, beta: float = 0.4,
+               uniform: bool = False) -> Dict[str, torch.Tensor]:
         """M transitions as a dict of tensors: actions [M,NA] int32, rewards [M,NA], dones [M] uint8,
         n [M] (live agents; -1 = invalid index), idx_out [M] int64, and per request obs / next_obs
         [M,NA,9R+1] (rows), xfrag / next_xfrag (fragments: the policy network's operand for a batch
@@ -125,7 +191,18 @@ class ReplayBuffer:
         prioritized sampler supply its own indices; None draws them on the device from
         (env.seed, draw), `draw` defaulting to a counter the buffer keeps.  The tensors are the
         buffer's own, overwritten by the next call -- or the caller's, through `out` (exactly the
-        keys to write)."""
+        keys to write).
+
+        A prioritized buffer with idx=None (and not `uniform`) draws entry i with probability
+        q_i / total from its tree instead (philox purpose 7 on (env.seed, draw)) and gathers those
+        entries on the same stream, with no host sync.  The dict then also holds prio_q [M] int32,
+        the sampled entries' fixed-point priorities, and weights [M] f32 = (q / total * N) ** -beta
+        divided by the batch's largest weight, N = len(self), computed in float64 from the exact
+        integers (`beta`: RLlib's prioritized_replay_beta); `self.prio_total` [1] int64 is the
+        total that launch read.  RLlib normalises by the weight of the
+        smallest priority in the whole buffer rather than in the batch; the two differ by one
+        common factor per batch, which rescales that batch's loss and nothing else.  `idx=...` and
+        `uniform=True` are the plain paths above, whatever the buffer."""
         e = self.env
         M = int(M)
         if M < 0:
@@ -142,11 +219,7 @@ class ReplayBuffer:
                     keys += pair
             t = {}
             for k in keys:
-                shape, dt = shapes[k]
-                if (k, M) not in self._out:
-                    self._out = {kk: v for kk, v in self._out.items() if kk[0] != k}   # one size kept per key
-                    self._out[(k, M)] = torch.empty(shape, dtype=dt, device=e.device)
-                t[k] = self._out[(k, M)]
+                t[k] = self._own(k, M, *shapes[k])
         else:
             t = dict(out)
             for k, v in t.items():
@@ -164,11 +237,24 @@ class ReplayBuffer:
         elif draw is None:
             draw = self._draw
             self._draw += 1
+        draw = int(draw or 0) & 0xFFFFFFFFFFFFFFFF
+        by_priority = self.prioritized and idx is None and not uniform
+        if by_priority:
+            t["prio_q"] = self._own("prio_q", M, (M,), torch.int32)
+            if M:
+                ix = self._own("prio_idx", M, (M,), torch.int64)
+                self._prio_call("wh_replay_prio_sample", M, None, e.seed, draw, ix.data_ptr(),
+                                t["prio_q"].data_ptr(), self.prio_total.data_ptr(), e.stream)
+            # (q / total * N) ** -beta over the batch's largest such weight: N / total is common to
+            # both and cancels, leaving (q / the batch's smallest q) ** -beta -- half the small
+            # launches.  (An empty tree gives q = 0 throughout: weights 1 for its n = -1 samples.)
+            q = t["prio_q"].clamp(min=1).to(torch.float64)
+            t["weights"] = ((q / q.min()) ** -float(beta) if M else q).to(torch.float32)
         if M == 0:
             return t
         p = {k: (t[k].data_ptr() if k in t else None) for k in shapes}
         batch = nat.WhReplayBatch(p["obs"], p["next_obs"], p["xfrag"], p["next_xfrag"], p["state"], p["next_state"],
                                   p["actions"], p["rewards"], p["dones"], p["n"], p["idx_out"])
-        e._call("wh_replay_gather", ctypes.byref(self._ring), self._filled, M, e._ptr(ix), e.seed,
-                int(draw or 0) & 0xFFFFFFFFFFFFFFFF, ctypes.byref(batch), e.stream)
+        e._call("wh_replay_gather", ctypes.byref(self._ring), self._filled, M, e._ptr(ix), e.seed, draw,
+                ctypes.byref(batch), e.stream)
         return t
