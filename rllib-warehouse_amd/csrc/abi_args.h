@@ -213,6 +213,45 @@ inline int sampler_rollout_call(StepCall* c, const wh_config* cfg, int64_t B, ui
   return finish(c, cfg);
 }
 
+// ----------------------------------------------------------------------------- pack, reset, observe
+// The config first, as everywhere.  A *_call that answers WH_OK for an empty batch (B == 0) has
+// looked at no pointer: the back end returns after its own refusals, without running anything.
+
+// a 64-bit seed or draw counter as the two 32-bit words of a Philox key or counter
+inline uint32_t lo32(uint64_t v) { return (uint32_t)(v & 0xFFFFFFFFu); }
+inline uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
+
+// wh_pack, wh_unpack (`state` and the eight canonical arrays, all required): the empty batch is
+// accepted before B < 0 and the pointers are looked at
+inline int pack_call(Shape* g, const wh_config* cfg, int64_t B, const void* state, const void* pos,
+                     const void* agent_target, const void* pickup_target, const void* pickup_timer, const void* t,
+                     const void* n, const void* fresh, const void* episode) {
+  const int rc = check_config(cfg, g);
+  if (rc || B == 0) return rc;
+  return (B < 0 || !pos || !agent_target || !pickup_target || !pickup_timer || !t || !n || !fresh || !episode || !state)
+             ? WH_EINVAL : WH_OK;
+}
+
+// wh_reset: injected draws come whole (spawn, pickups, targets; n is optional)
+inline int reset_call(Shape* g, const wh_config* cfg, int64_t B, const uint32_t* state, const wh_reset_draws* draws) {
+  const int rc = check_config(cfg, g);
+  if (rc) return rc;
+  if (B < 0) return WH_EINVAL;
+  if (B == 0) return WH_OK;
+  if (!state) return WH_EINVAL;
+  return (draws && (!draws->spawn || !draws->pickups || !draws->targets)) ? WH_EINVAL : WH_OK;
+}
+
+// wh_observe (xfrag = NULL), wh_observe_x (rows to `obs`, to the 16-byte aligned `xfrag`, or both)
+inline int observe_call(Shape* g, const wh_config* cfg, int64_t B, const uint32_t* state, const float* obs,
+                        const void* xfrag) {
+  const int rc = check_config(cfg, g);
+  if (rc) return rc;
+  if (B < 0) return WH_EINVAL;
+  if (B == 0) return WH_OK;
+  return (!state || (!obs && !xfrag) || (uintptr_t)xfrag % 16 != 0) ? WH_EINVAL : WH_OK;
+}
+
 // ----------------------------------------------------------------------------- replay ring
 // The same order as the step family: the entry point's own options and required pointers, the
 // config, the state pointer (put) or the alignment that depends on the config (gather), B < 0.
@@ -281,6 +320,17 @@ inline int prio_shape(int64_t count, PrioShape* s) {
     s->off[s->levels] = s->node_words;
     s->node_words += pad16(n);
   } while (n > 1);
+  return WH_OK;
+}
+
+// wh_replay_prio_query, whole: it asks nothing of a back end
+inline int prio_query(int64_t count, int64_t* leaf_words, int64_t* node_words, int32_t* levels) {
+  PrioShape s;
+  const int rc = prio_shape(count, &s);
+  if (rc) return rc;
+  if (leaf_words) *leaf_words = s.leaf_words;
+  if (node_words) *node_words = s.node_words;
+  if (levels) *levels = s.levels;
   return WH_OK;
 }
 

@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "abi_args.h"
+#include "geometry.h"
 #include "warehouse_amd.h"
 
 namespace {
@@ -53,32 +54,23 @@ int make_geo(const wh_abi::Shape& shape, Geo* g) {
   static_cast<wh_abi::Shape&>(*g) = shape;
   static_assert(kMaxD >= 32, "the ABI's largest area");
   if (g->P > kMaxP || g->DP > kMaxP || g->NA > kMaxA) return WH_ENOTSUP;
+  if (wh_geo::racks_overlap(g->racks, g->NR)) return WH_ENOTSUP;
   memset(g->cell, -1, sizeof(g->cell));
-  // pickup points: for x in racks, for y in racks: (x-1, y-1), (x, y-1), (x-1, y), (x, y)
-  int j = 0;
-  for (int ix = 0; ix < g->NR; ++ix)
-    for (int iy = 0; iy < g->NR; ++iy)
-      for (int q = 0; q < 4; ++q, ++j) {
-        const int x = g->racks[ix] - 1 + (q & 1), y = g->racks[iy] - 1 + (q >> 1);
-        if (g->cell[x][y] >= 0) return WH_ENOTSUP;   // overlapping racks
-        g->cell[x][y] = (int8_t)j;
-        g->px[j] = x;
-        g->py[j] = y;
-      }
-  // delivery points: for v in 2..D-3: (v, 0), (0, v), (v, D-1), (D-1, v)
-  for (int d = 0; d < g->DP; ++d) {
-    const int v = 2 + d / 4, side = d % 4;
-    g->dxc[d] = (side & 1) ? (side == 3 ? g->D - 1 : 0) : v;
-    g->dyc[d] = (side & 1) ? v : (side == 2 ? g->D - 1 : 0);
+  for (int j = 0; j < g->P; ++j) {
+    const wh_geo::Cell c = wh_geo::pickup_cell(g->racks, g->NR, j);
+    g->cell[c.x][c.y] = (int8_t)j;
+    g->px[j] = c.x;
+    g->py[j] = c.y;
   }
-  g->NV = 0;
-  for (int x = 1; x < g->D - 1; ++x)
-    for (int y = 1; y < g->D - 1; ++y)
-      if (g->cell[x][y] < 0) {
-        g->vx[g->NV] = x;
-        g->vy[g->NV] = y;
-        ++g->NV;
-      }
+  for (int d = 0; d < g->DP; ++d) {
+    const wh_geo::Cell c = wh_geo::delivery_cell(d, g->D);
+    g->dxc[d] = c.x;
+    g->dyc[d] = c.y;
+  }
+  g->NV = wh_geo::spawn_cells(g->racks, g->NR, g->D, [g, i = 0](int x, int y) mutable {
+    g->vx[i] = x;
+    g->vy[i++] = y;
+  });
   return WH_OK;
 }
 
@@ -86,14 +78,6 @@ int make_geo(const wh_config* c, Geo* g) {
   wh_abi::Shape shape;
   const int rc = wh_abi::check_config(c, &shape);
   return rc ? rc : make_geo(shape, g);
-}
-
-// delivery cell -> delivery index (the inverse of the table above)
-int delivery_index(int x, int y, int D) {
-  if (y == 0) return 4 * (x - 2);
-  if (x == 0) return 4 * (y - 2) + 1;
-  if (y == D - 1) return 4 * (x - 2) + 2;
-  return 4 * (y - 2) + 3;
 }
 
 // ----------------------------------------------------------------------------- philox
@@ -151,7 +135,7 @@ void load(const Geo& g, const uint32_t* st, int64_t B, int64_t e, Env& s) {
     s.x[i] = (int)(w & 0xFFu);
     s.y[i] = (int)((w >> 16) & 0xFFu);
     const uint32_t dx = (w >> 8) & 0xFFu, dy = w >> 24;
-    s.tg[i] = (dx == 0xFFu) ? -1 : delivery_index((int)dx, (int)dy, g.D);
+    s.tg[i] = (dx == 0xFFu) ? -1 : wh_geo::delivery_index((int)dx, (int)dy, g.D);
   }
   const int PW = g.P / 4;
   for (int w = 0; w < PW; ++w) {
@@ -517,9 +501,6 @@ void fold_episode(const wh_episode_stats* st, uint32_t n, uint32_t ret) {
   }
 }
 
-uint32_t keys_lo(uint64_t seed) { return (uint32_t)(seed & 0xFFFFFFFFu); }
-uint32_t keys_hi(uint64_t seed) { return (uint32_t)(seed >> 32); }
-
 // ----------------------------------------------------------------------------- the step family
 // One env of a checked step-family call (abi_args.h): c.steps times [policy ->] step -> rewards /
 // dones -> episode-return fold -> auto-reset on an unmasked env, then its rows.  wh_step (phases,
@@ -527,7 +508,7 @@ uint32_t keys_hi(uint64_t seed) { return (uint32_t)(seed >> 32); }
 // rows) and wh_sampler_step (a policy, rows) are this with the options each one sets.
 void drive_env(const Geo& g, const wh_abi::StepCall& c, int64_t e) {
   const int64_t B = c.B;
-  const uint32_t k0 = keys_lo(c.seed), k1 = keys_hi(c.seed), gid = (uint32_t)(c.env_offset + e);
+  const uint32_t k0 = wh_abi::lo32(c.seed), k1 = wh_abi::hi32(c.seed), gid = (uint32_t)(c.env_offset + e);
   Env s;
   load(g, c.state, B, e, s);
   if (!c.mask || c.mask[e]) {
@@ -606,11 +587,8 @@ int wh_pack(const wh_config* cfg, int64_t B, const int32_t* pos, const int32_t* 
             const uint8_t* fresh, const uint32_t* episode, uint32_t* state, void* stream) {
   (void)stream;
   Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B == 0) return WH_OK;
-  if (B < 0 || !pos || !agent_target || !pickup_target || !pickup_timer || !t || !n || !fresh || !episode || !state)
-    return WH_EINVAL;
+  int rc = wh_abi::pack_call(&g, cfg, B, state, pos, agent_target, pickup_target, pickup_timer, t, n, fresh, episode);
+  if (rc || (rc = make_geo(wh_abi::Shape(g), &g)) || B == 0) return rc;
   for (int64_t e = 0; e < B; ++e) {   // out-of-range canonical values are clamped (as wh_pack on the device)
     Env s{};
     s.t = (uint32_t)t[e] & 0xFFFFu;
@@ -638,11 +616,8 @@ int wh_unpack(const wh_config* cfg, int64_t B, const uint32_t* state, int32_t* p
               uint32_t* episode, void* stream) {
   (void)stream;
   Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B == 0) return WH_OK;
-  if (B < 0 || !pos || !agent_target || !pickup_target || !pickup_timer || !t || !n || !fresh || !episode || !state)
-    return WH_EINVAL;
+  int rc = wh_abi::pack_call(&g, cfg, B, state, pos, agent_target, pickup_target, pickup_timer, t, n, fresh, episode);
+  if (rc || (rc = make_geo(wh_abi::Shape(g), &g)) || B == 0) return rc;
   for (int64_t e = 0; e < B; ++e) {
     Env s;
     load(g, state, B, e, s);
@@ -668,12 +643,8 @@ int wh_reset(const wh_config* cfg, int64_t B, uint32_t* state, const uint8_t* ma
              int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream) {
   (void)stream;
   Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  if (!state) return WH_EINVAL;
-  if (draws && (!draws->spawn || !draws->pickups || !draws->targets)) return WH_EINVAL;
+  int rc = wh_abi::reset_call(&g, cfg, B, state, draws);
+  if (rc || (rc = make_geo(wh_abi::Shape(g), &g)) || B == 0) return rc;
 #pragma omp parallel for schedule(static) if (B >= 1024)
   for (int64_t e = 0; e < B; ++e) {
     if (mask && !mask[e]) continue;
@@ -682,7 +653,7 @@ int wh_reset(const wh_config* cfg, int64_t B, uint32_t* state, const uint8_t* ma
     if (draws)
       reset_injected(g, s, e, *draws);
     else
-      reset_philox(g, s, keys_lo(seed), keys_hi(seed), (uint32_t)(env_offset + e), variable_n != 0);
+      reset_philox(g, s, wh_abi::lo32(seed), wh_abi::hi32(seed), (uint32_t)(env_offset + e), variable_n != 0);
     store(g, state, B, e, s);
   }
   return WH_OK;
@@ -698,11 +669,8 @@ int wh_step(const wh_config* cfg, int64_t B, uint32_t* state, const int32_t* act
 
 int wh_observe(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void*) {
   Geo g;
-  const int rc = make_geo(cfg, &g);
-  if (rc) return rc;
-  if (B < 0) return WH_EINVAL;
-  if (B == 0) return WH_OK;
-  if (!state || !obs) return WH_EINVAL;
+  int rc = wh_abi::observe_call(&g, cfg, B, state, obs, nullptr);
+  if (rc || (rc = make_geo(wh_abi::Shape(g), &g)) || B == 0) return rc;
 #pragma omp parallel for schedule(static) if (B >= 1024)
   for (int64_t e = 0; e < B; ++e) {
     Env s;
@@ -722,7 +690,7 @@ int wh_policy(const wh_config* cfg, int64_t B, const uint32_t* state, int32_t po
   for (int64_t e = 0; e < B; ++e) {
     Env s;
     load(g, state, B, e, s);
-    policy_env(g, s, policy, p, keys_lo(seed), keys_hi(seed), (uint32_t)(env_offset + e), actions + e * g.NA);
+    policy_env(g, s, policy, p, wh_abi::lo32(seed), wh_abi::hi32(seed), (uint32_t)(env_offset + e), actions + e * g.NA);
   }
   return WH_OK;
 }
@@ -807,7 +775,7 @@ int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring
   if (B == 0 || M == 0) return WH_OK;
   const int words = g.words, na = g.NA;
   const int64_t row = (int64_t)na * g.L;
-  const uint32_t k0 = keys_lo(seed), k1 = keys_hi(seed);
+  const uint32_t k0 = wh_abi::lo32(seed), k1 = wh_abi::hi32(seed);
 #pragma omp parallel for schedule(static) if (M >= 1024)
   for (int64_t m = 0; m < M; ++m) {
     int64_t ix;
@@ -853,13 +821,7 @@ static void prio_add(const wh_replay_prio* t, const wh_abi::PrioShape& s, int64_
 }
 
 int wh_replay_prio_query(int64_t count, int64_t* leaf_words, int64_t* node_words, int32_t* levels) {
-  wh_abi::PrioShape s;
-  const int rc = wh_abi::prio_shape(count, &s);
-  if (rc) return rc;
-  if (leaf_words) *leaf_words = s.leaf_words;
-  if (node_words) *node_words = s.node_words;
-  if (levels) *levels = s.levels;
-  return WH_OK;
+  return wh_abi::prio_query(count, leaf_words, node_words, levels);
 }
 
 int wh_replay_prio_fill(const wh_replay_prio* tree, int64_t first, int64_t n, int32_t mode, uint32_t q, void*) {
@@ -905,7 +867,7 @@ int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t*
   wh_abi::PrioShape s;
   const int rc = wh_abi::prio_sample_call(&s, tree, M, idx_out);
   if (rc || M == 0) return rc;
-  const uint32_t k0 = keys_lo(seed), k1 = keys_hi(seed);
+  const uint32_t k0 = wh_abi::lo32(seed), k1 = wh_abi::hi32(seed);
   const uint64_t total = tree->node[s.off[s.levels]];
   if (total_out) *total_out = total;
   for (int64_t m = 0; m < M; ++m) {

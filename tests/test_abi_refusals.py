@@ -1,11 +1,15 @@
 """The two libraries behind include/warehouse_amd.h refuse the same calls: one table of calls to
-every step-family entry point with the return code the header's contract gives, run against the
-gfx950 library and the host engine.  The argument rules are written once (csrc/abi_args.h), so both
-answer alike; the host engine answers WH_ENOTSUP for the entries it does not implement.
+every step-family entry point and to wh_pack / wh_unpack / wh_reset / wh_observe(_x), with the return
+code the header's contract gives, run against the gfx950 library and the host engine.  The argument
+rules are written once (csrc/abi_args.h), so both answer alike; the host engine answers WH_ENOTSUP
+for the entries it does not implement.
 
 No call gets as far as a launch: a batch of B > 0 envs appears only where the call is refused on
 the host side first (its pointers are never dereferenced), every call that is accepted is an empty
-batch.  So the table runs the same with or without a GPU."""
+batch.  So the table runs the same with or without a GPU.
+
+Rows that fit only one of the pack / reset / observe entries, and the one config on which the two
+libraries answer differently (racks that overlap), are in ENTRY_ROWS below the table."""
 import ctypes
 
 import pytest
@@ -14,7 +18,7 @@ from warehouse import _native as nat
 
 OK, EINVAL, ENOTSUP = nat.WH_OK, nat.WH_EINVAL, nat.WH_ENOTSUP
 
-# argument names of every step-family entry point, in the header's order
+# argument names of every entry point of the table, in the header's order
 _ROLLOUT = ("cfg B state steps policy p rewards dones returns stats autoreset variable_n seed env_offset")
 ENTRIES = {
     "wh_step": "cfg B state actions order order_len rewards dones regen n_inactive phase seed env_offset stream",
@@ -32,13 +36,21 @@ ENTRIES = {
     "wh_rollout_wide": _ROLLOUT + " lanes stream",
     "wh_vector_step_wide": "cfg B state actions mask rewards dones obs stats autoreset variable_n seed env_offset "
                            "lanes stream",
+    "wh_pack": "cfg B pos agent_target pickup_target pickup_timer t n fresh episode state stream",
+    "wh_unpack": "cfg B state pos agent_target pickup_target pickup_timer t n fresh episode stream",
+    "wh_reset": "cfg B state mask draws variable_n seed env_offset stream",
+    "wh_observe": "cfg B state rows stream",
+    "wh_observe_x": "cfg B state rows xrows stream",
 }
 ENTRIES = {k: tuple(v.split()) for k, v in ENTRIES.items()}
 # device-only entries: the host engine answers WH_ENOTSUP whatever the arguments
 HOST_ENOTSUP = {"wh_rollout_prepare", "wh_vector_step_x", "wh_sampler_step_to", "wh_step_wide", "wh_rollout_wide",
-                "wh_vector_step_wide"}
+                "wh_vector_step_wide", "wh_observe_x"}
+# (wh_observe's rows are "rows" / "xrows" here: the table's obs and xfrag rows state the step family's
+# rules -- obs optional, xfrag required and checked for an empty batch too -- which are not wh_observe_x's)
+CANONICAL = ("pos", "agent_target", "pickup_target", "pickup_timer", "t", "n", "fresh", "episode")
 POINTERS = {"state", "actions", "order", "mask", "rewards", "dones", "returns", "regen", "n_inactive", "obs", "xfrag",
-            "state_out"}
+            "state_out", "rows", "xrows", *CANONICAL}
 DUMMY = 4096   # a 16-byte aligned address that a refused call never dereferences
 NA = 4         # agent slots of the base config (Small)
 
@@ -161,13 +173,13 @@ def call(lib, name, over, B, steps):
     """One call: every pointer a dummy (NULL for an empty batch), every option valid, then `over`."""
     vals = dict(cfg=config(), B=B, steps=steps, policy=nat.WH_POLICY_GREEDY, p=0.25, stats=None, autoreset=1,
                 variable_n=0, seed=1234, env_offset=0, order_len=0, phase=nat.WH_PHASE_ALL, lanes=nat.WH_WIDE_LANES,
-                stream=None)
+                stream=None, draws=None)
     for k in POINTERS:
         vals[k] = DUMMY if B > 0 else None
     handle = ctypes.c_void_p(0x1)
     vals["out"] = ctypes.byref(handle)
     vals.update({k: v for k, v in over.items() if k not in ("B", "steps")})
-    for k in ("cfg", "stats"):
+    for k in ("cfg", "stats", "draws"):
         if vals[k] is not None:
             vals[k] = ctypes.byref(vals[k])
     rc = getattr(lib, name)(*[vals[a] for a in ENTRIES[name]])
@@ -198,6 +210,66 @@ def mismatches(lib, name, host):
 def test_refusals(engine, name):
     host = engine == "host"
     bad = mismatches(nat.host_lib() if host else nat.lib(), name, host)
+    assert not bad, "\n".join(bad)
+
+
+# ---- rows of one entry point: (entry, what is wrong, the arguments, B, the device library's code, the
+# host engine's).  The codes were read off both libraries before abi_args.h took these four entries
+# over (pack_call / reset_call / observe_call), and are what they answered then.
+def partial_draws(*given):
+    return nat.WhResetDraws(*[DUMMY if k in given else None for k in ("spawn", "pickups", "targets", "n")])
+
+
+OVERLAP = dict(racks=(4, 5))   # rack cells {3, 4} and {4, 5}: two pickup points on one cell
+ENTRY_ROWS = []
+for _name in ("wh_pack", "wh_unpack"):
+    ENTRY_ROWS += [(_name, f"missing {k}", {k: None}, 8, EINVAL, EINVAL) for k in CANONICAL + ("state",)]
+    ENTRY_ROWS += [
+        # the empty batch is accepted before B < 0 and the pointers are looked at, the config is not
+        (_name, "empty batch, no pointers", {}, 0, OK, OK),
+        (_name, "B < 0 and a rack on the border", dict(cfg=config(racks=(1, 8))), -1, ENOTSUP, ENOTSUP),
+        # the device's pack kernels need no tables, and an empty batch launches nothing
+        (_name, "overlapping racks, empty batch", dict(cfg=config(**OVERLAP)), 0, OK, ENOTSUP),
+        (_name, "overlapping racks", dict(cfg=config(**OVERLAP)), 8, None, ENOTSUP),
+    ]
+ENTRY_ROWS += [
+    ("wh_reset", "draws without pickups", dict(draws=partial_draws("spawn", "targets")), 8, EINVAL, EINVAL),
+    ("wh_reset", "draws without targets", dict(draws=partial_draws("spawn", "pickups", "n")), 8, EINVAL, EINVAL),
+    ("wh_reset", "draws without spawn", dict(draws=partial_draws("pickups", "targets")), 8, EINVAL, EINVAL),
+    ("wh_reset", "empty draws", dict(draws=partial_draws()), 8, EINVAL, EINVAL),
+    ("wh_reset", "partial draws, empty batch", dict(draws=partial_draws("spawn")), 0, OK, OK),
+    ("wh_reset", "partial draws and B < 0", dict(draws=partial_draws("spawn")), -1, EINVAL, EINVAL),
+    ("wh_reset", "no mask (optional), empty batch", dict(mask=None), 0, OK, OK),
+    ("wh_observe", "missing rows", dict(rows=None), 8, EINVAL, EINVAL),
+    ("wh_observe", "missing rows, empty batch", dict(rows=None), 0, OK, OK),
+    ("wh_observe_x", "neither rows nor xrows", dict(rows=None, xrows=None), 8, EINVAL, ENOTSUP),
+    ("wh_observe_x", "misaligned xrows", dict(xrows=DUMMY + 4), 8, EINVAL, ENOTSUP),
+    ("wh_observe_x", "misaligned xrows, no rows", dict(rows=None, xrows=DUMMY + 8), 8, EINVAL, ENOTSUP),
+    ("wh_observe_x", "misaligned xrows and B < 0", dict(xrows=DUMMY + 4), -1, EINVAL, ENOTSUP),
+    # (unlike wh_vector_step_x, whose xfrag is checked whatever the batch)
+    ("wh_observe_x", "misaligned xrows, empty batch", dict(xrows=DUMMY + 4), 0, OK, ENOTSUP),
+]
+for _name in ("wh_reset", "wh_observe", "wh_observe_x"):
+    ENTRY_ROWS += [
+        # racks that overlap are a back end's refusal: the device library meets them when it builds the
+        # tables of a batch that launches (not run here), the host engine in every call
+        (_name, "overlapping racks, empty batch", dict(cfg=config(**OVERLAP)), 0, OK, ENOTSUP),
+        (_name, "overlapping racks", dict(cfg=config(**OVERLAP)), 8, None, ENOTSUP),
+    ]
+
+
+@pytest.mark.parametrize("engine", ["device", "host"])
+def test_entry_rows(engine):
+    host = engine == "host"
+    lib = nat.host_lib() if host else nat.lib()
+    bad = []
+    for name, what, over, B, dev_code, host_code in ENTRY_ROWS:
+        want = host_code if host else dev_code
+        if want is None:   # a call this library would launch
+            continue
+        got = call(lib, name, over, B, 1)
+        if got != want:
+            bad.append(f"{name}({what}; B={B}): returned {got}, contract {want}")
     assert not bad, "\n".join(bad)
 
 

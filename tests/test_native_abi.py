@@ -46,7 +46,10 @@ def test_library_built_from_this_tree():
     assert _native.file_version(_native.LIB_PATH) == (sha, "")
     assert _native.file_version(os.path.join(ROOT, "build_ab", "check.so")) == (sha, _native.CHECK_VARIANT)
     names = [os.path.basename(p) for p in _native.hashed_files()]
-    assert {"Makefile", "version.cpp", "warehouse_amd.hip", "policy_mlp.hip", "philox.h", "abi_args.h", "warehouse_amd.h"} <= set(names)
+    assert {"Makefile", "version.cpp", "warehouse_amd.hip", "policy_mlp.hip", "philox.h", "abi_args.h", "warehouse_amd.h",
+            # the kernel headers warehouse_amd.hip is made of, and the geometry both engines share
+            "device_vocab.h", "reset.h", "policy.h", "step_env.h", "step_params.h", "step_wide.h", "step_loops.h",
+            "observe.h", "replay.h", "prio.h", "sampler.h", "pack.h", "geometry.h"} <= set(names)
 
 
 def _probe_version(tmp_path, *make_args):
