@@ -302,6 +302,18 @@ int wh_mlp_query(const wh_mlp_desc* d, int64_t* packed_bytes);
 int wh_mlp_pack(const wh_mlp_desc* d, const float* w0, const float* b0, const float* w1,
                 const float* b1, const float* w2, const float* b2, void* packed);
 
+/* wh_mlp_pack with w0..b2 in DEVICE memory (same layouts), as kernels on `stream`: no host copy of the
+ * weights, no synchronisation.  The blob is byte-for-byte the one wh_mlp_pack makes from the same values
+ * (both run the same index maps and the same integer round-to-nearest-even), so a learner that keeps
+ * its parameters on the card refreshes a rollout network, or a Q network, without leaving the stream.
+ * One launch.  The first call for a shape and device uploads that shape's operand table (a few KB):
+ * that call allocates and copies synchronously and must not happen inside a stream capture; every
+ * later call for the shape on that device only enqueues.  `packed`: wh_mlp_query bytes, 16-byte
+ * aligned (else WH_EINVAL).  d == NULL or any pointer NULL: WH_EINVAL; an unknown shape: WH_ENOTSUP.
+ * Device only. */
+int wh_mlp_pack_device(const wh_mlp_desc* d, const float* w0, const float* b0, const float* w1,
+                       const float* b1, const float* w2, const float* b2, void* packed, void* stream);
+
 /* obs [rows, in_dim] f32 -> logits [rows, 9] f32 and/or actions [rows] int32 (either may be NULL,
  * not both).  explore = 0: argmax, first maximum wins; explore = 1: Gumbel-max sample of
  * Categorical(logits), noise from philox (seed; counter row, step, purpose 5). */
@@ -432,6 +444,39 @@ int wh_replay_prio_update(const wh_replay_prio* tree, int64_t M, const int64_t* 
  * q_out = 0, which wh_replay_gather turns into n = -1 and a zero sample.  M = 0 launches nothing. */
 int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t* u, uint64_t seed, uint64_t draw,
                           int64_t* idx_out, uint32_t* q_out, uint64_t* total_out, void* stream);
+
+/* SAC TD TARGETS: RLlib's discrete SAC (sac_tf_policy, discrete branch) from logits, one launch.  The
+ * Q_model of the experiment YAMLs has the policy_model's shape, so the five [rows, 9] arrays below
+ * are what wh_mlp_forward / wh_mlp_forward_x write for the policy, the two target Q networks (on the
+ * next-side operand) and the two Q networks (on the obs-side operand).  For row r = m * NA + i, all
+ * in f32, sums over o = 0..8 in ascending order:
+ *   lse   = zmax + log(sum_o exp(pi_next[r,o] - zmax)),  zmax = max_o pi_next[r,o]
+ *   logp  = pi_next[r,o] - lse ;  p = exp(logp)
+ *   v     = sum_o p[o] * (min(q1t_next[r,o], q2t_next[r,o]) - alpha * logp[o])     (q2t NULL: q1t alone)
+ *   y     = rewards[m,i] + discount * ((mask_dones && dones[m]) ? 0 : v)
+ *   a     = actions[m,i] if in 0..8 else 4          (the ring's rule for stray actions)
+ *   td_r  = (|q1[r,a] - y| + |q2[r,a] - y|) / 2     (q2 NULL: |q1[r,a] - y|)
+ *   td[m] = (sum_{i < n[m]} td_r[m,i]) / n[m]       (n NULL: NA;  n[m] <= 0: 0;  n[m] > NA: as NA)
+ * Rows i >= n[m], and every row of a sample with n[m] = -1 (wh_replay_gather's invalid index), write
+ * y = 0 and td_rows = 0.  td[m] is ONE priority per ring entry (an env-step, what
+ * wh_replay_prio_update takes): the mean of the TD errors of that entry's live agent rows.
+ * `discount` is gamma ** n_step, computed by the caller; mask_dones = 0 is what the YAMLs train with
+ * (no_done_at_end: true).  td[m] is summed inside one workgroup in ascending row order, without
+ * atomics: the result is deterministic.  Inputs are assumed finite; non-finite values propagate as
+ * IEEE arithmetic gives and are not part of the contract.
+ * WH_EINVAL: a == NULL, M < 0, NA outside 1 .. 16; and for M > 0: all three outputs NULL; pi_next,
+ * q1t_next, actions or rewards NULL; td_rows, td or q2 set without q1; mask_dones != 0 with dones
+ * NULL.  M = 0 launches nothing (WH_OK, no pointer looked at).  Both engines implement it. */
+typedef struct wh_sac_td_args {
+  const float *pi_next, *q1t_next, *q2t_next;   /* [M*NA, 9]; q2t_next may be NULL */
+  const float *q1, *q2;                         /* [M*NA, 9]; both NULL = targets only; q2 alone NULL = no twin */
+  const int32_t* actions;  const float* rewards;  /* [M, NA] */
+  const uint8_t* dones;    const int32_t* n;      /* [M]; either may be NULL */
+  float alpha, discount;   int32_t mask_dones;
+  float *y, *td_rows;      /* [M, NA] out; may be NULL */
+  float* td;               /* [M] out; may be NULL */
+} wh_sac_td_args;
+int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void* stream);
 
 /* Library build identification (e.g. "warehouse_amd gfx950 <date>"). */
 const char* wh_version(void);

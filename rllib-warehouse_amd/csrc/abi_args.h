@@ -364,6 +364,20 @@ inline int prio_sample_call(PrioShape* s, const wh_replay_prio* t, int64_t M, co
   return M < 0 ? WH_EINVAL : WH_OK;
 }
 
+// ----------------------------------------------------------------------------- SAC TD targets
+// wh_sac_td: the sizes first (a, M, NA), then -- for M > 0 only, as everywhere -- the pointers: at
+// least one output, the four required inputs, and what an output or option needs beside it.
+constexpr int32_t SAC_MAX_AGENTS = 16;
+
+inline int sac_td_call(int64_t M, int32_t NA, const wh_sac_td_args* a) {
+  if (!a || M < 0 || NA < 1 || NA > SAC_MAX_AGENTS) return WH_EINVAL;
+  if (M == 0) return WH_OK;
+  if (!a->y && !a->td_rows && !a->td) return WH_EINVAL;
+  if (!a->pi_next || !a->q1t_next || !a->actions || !a->rewards) return WH_EINVAL;
+  if ((a->td_rows || a->td || a->q2) && !a->q1) return WH_EINVAL;
+  return (a->mask_dones != 0 && !a->dones) ? WH_EINVAL : WH_OK;
+}
+
 // the quantisation rule, one for both engines (plain C++: also device code)
 #if defined(__HIPCC__)
 __host__ __device__

@@ -29,6 +29,7 @@
 
 #include "abi_args.h"
 #include "geometry.h"
+#include "sac_formula.h"
 #include "warehouse_amd.h"
 
 namespace {
@@ -900,6 +901,36 @@ int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t*
   return WH_OK;
 }
 
+// ---- SAC TD targets (include/warehouse_amd.h, SAC TD TARGETS): sac_formula.h's arithmetic, the
+// device's operation order, in a plain loop over the rows
+int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void*) {
+  const int rc = wh_abi::sac_td_call(M, NA, a);
+  if (rc || M == 0) return rc;
+  const bool twin = a->q2 != nullptr;
+  for (int64_t m = 0; m < M; ++m) {
+    const int nn = wh_sac::live_rows(a->n, m, NA);
+    const bool masked = a->mask_dones != 0 && a->dones[m] != 0;
+    float sum = 0.0f;
+    for (int i = 0; i < NA; ++i) {
+      const int64_t row = m * NA + i, e = row * wh_sac::OUT;
+      float y = 0.0f, tdr = 0.0f;
+      if (i < nn) {
+        const float v = wh_sac::soft_value(a->pi_next + e, a->q1t_next + e, a->q2t_next ? a->q2t_next + e : nullptr, a->alpha);
+        y = wh_sac::target(a->rewards[row], a->discount, masked, v);
+        if (a->q1) {
+          const int act = wh_sac::taken_action(a->actions[row]);
+          tdr = wh_sac::td_row(a->q1[e + act], twin ? a->q2[e + act] : 0.0f, twin, y);
+        }
+      }
+      if (a->y) a->y[row] = y;
+      if (a->td_rows) a->td_rows[row] = tdr;
+      sum += tdr;
+    }
+    if (a->td) a->td[m] = wh_sac::td_mean(sum, nn);
+  }
+  return WH_OK;
+}
+
 // ---- what the CPU has no use for: the policy network and its fragment operand (device formats),
 // the two-stream sampler step, prepared launches, assert-mode counters, and the 16-lanes-per-env
 // form (csrc/step_wide.h: the host engine has no lanes)
@@ -919,6 +950,8 @@ int wh_launch_free(wh_launch* launch) { return launch ? WH_EINVAL : WH_OK; }
 int wh_mlp_query(const wh_mlp_desc*, int64_t*) { return WH_ENOTSUP; }
 int wh_mlp_pack(const wh_mlp_desc*, const float*, const float*, const float*, const float*, const float*,
                 const float*, void*) { return WH_ENOTSUP; }
+int wh_mlp_pack_device(const wh_mlp_desc*, const float*, const float*, const float*, const float*, const float*,
+                       const float*, void*, void*) { return WH_ENOTSUP; }
 int wh_mlp_forward(const wh_mlp_desc*, const void*, int64_t, const float*, float*, int32_t*, int32_t, uint64_t,
                    uint32_t, void*) { return WH_ENOTSUP; }
 int wh_mlp_forward_x(const wh_mlp_desc*, const void*, int64_t, const void*, float*, int32_t*, int32_t, uint64_t,

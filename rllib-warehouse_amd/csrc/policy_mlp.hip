@@ -27,6 +27,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 #include "philox.h"
@@ -902,193 +904,39 @@ __global__ __launch_bounds__(256) void k_mlp_f32(MlpArgs a) {
   emit_logits(lg, gb + N::H0 + N::H1, row, live, h, a);
 }
 
+// ------------------------------------------------------------------------------------- packing
+// the three blob formats (Map32 / Map16 / MapF), the host packer and the device packer (k_mlp_pack)
+#include "mlp_pack.h"
+
 // ------------------------------------------------------------------------------------- host
-uint16_t to_bf16(float f) {   // round to nearest even (NaN not expected in weights)
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-float from_bf16(uint16_t b) {
-  const uint32_t u = (uint32_t)b << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-
-template <class N>
-std::vector<uint8_t> pack(const float* w0, const float* b0, const float* w1, const float* b1,
-                          const float* w2, const float* b2) {
-  std::vector<uint8_t> blob(N::BYTES, 0);
-  uint16_t* f = reinterpret_cast<uint16_t*>(blob.data());
-  // operand `op` = one MFMA A operand = 64 lanes x 8 bf16; the kernel reads lane l's 16 bytes
-  auto put = [&](int64_t op, int lane, int j, float v) { f[(op * 64 + lane) * 8 + j] = to_bf16(v); };
-  // k order of an accumulator-as-operand fragment (layers 1, 2)
-  auto kperm = [](int i, int s, int l, int j) { return 32 * i + 16 * s + 8 * (j >> 2) + 4 * (l >> 5) + (j & 3); };
-  auto w1op = [&](int64_t op, int n, int t, int s) {   // W1 [H1][H0]: row tile n, k-step (t, s)
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) put(op, l, j, w1[(int64_t)(32 * n + (l & 31)) * N::H0 + kperm(t, s, l, j)]);
-  };
-  auto w2op = [&](int64_t op, int n, int s) {          // W2 [9][H1]: k-step (n, s), rows padded to 32
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int o = l & 31;
-        put(op, l, j, o < N::OUT ? w2[(int64_t)o * N::H1 + kperm(n, s, l, j)] : 0.0f);
-      }
-  };
-  for (int c = 0; c < N::L0C; ++c)
-    for (int m = 0; m < N::L0T; ++m) {
-      const int t = c * N::L0T + m;                // layer-0 row tile
-      const int64_t base = N::chunk_off(c) + (int64_t)m * N::U0;
-      for (int q = 0; q < N::KQ0; ++q)             // W0 [H0][IN], natural k order (X^T from memory)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 8; ++j) {
-            const int k = 16 * q + 8 * (l >> 5) + j, o = 32 * t + (l & 31);
-            const float bh = from_bf16(to_bf16(b0[o]));        // b0 = hi + lo, both bf16
-            const float v = k < N::IN ? w0[(int64_t)o * N::IN + k] : k == N::IN ? bh : k == N::IN + 1 ? b0[o] - bh : 0.0f;
-            put(base + q, l, j, v);
-          }
-      if (N::MODE == 1)                             // this tile's k-steps of every layer-1 row tile
-        for (int n = 0; n < N::T1; ++n)
-          for (int s = 0; s < 2; ++s) w1op(base + N::KQ0 + 2 * n + s, n, t, s);
-    }
-  if (N::MODE == 0) {
-    for (int d = 0; d < N::L1C; ++d)
-      for (int nn = 0; nn < N::L1T; ++nn) {
-        const int n = d * N::L1T + nn;             // layer-1 row tile
-        const int64_t base = N::chunk_off(N::L0C + d) + (int64_t)nn * N::U1;
-        for (int t = 0; t < N::T0; ++t)
-          for (int s = 0; s < 2; ++s) w1op(base + 2 * t + s, n, t, s);
-        for (int s = 0; s < 2; ++s) w2op(base + 2 * N::T0 + s, n, s);
-      }
-  } else {
-    for (int n = 0; n < N::T1; ++n)
-      for (int s = 0; s < 2; ++s) w2op(N::chunk_off(N::L0C) + 2 * n + s, n, s);
-  }
-  float* bias = reinterpret_cast<float*>(blob.data() + N::BIAS_OFF);
-  memcpy(bias, b0, 4 * N::H0);
-  memcpy(bias + N::H0, b1, 4 * N::H1);
-  memcpy(bias + N::H0 + N::H1, b2, 4 * N::OUT);
-  return blob;
-}
-
-// Net16 blob: operands of 16 rows x 32 k, lane l = row l&15, k 8(l>>4)+j; layer-0 k order natural
-// (X^T from memory), layers 1-2 in kperm16 order (the accumulator-as-operand fragments).
-template <class N>
-std::vector<uint8_t> pack16(const float* w0, const float* b0, const float* w1, const float* b1,
-                            const float* w2, const float* b2) {
-  std::vector<uint8_t> blob(N::BYTES, 0);
-  uint16_t* f = reinterpret_cast<uint16_t*>(blob.data());
-  auto put = [&](int64_t op, int lane, int j, float v) { f[(op * 64 + lane) * 8 + j] = to_bf16(v); };
-  auto kperm16 = [](int m, int l, int j) { const int g = l >> 4; return 32 * m + (j < 4 ? 4 * g + j : 16 + 4 * g + j - 4); };
-  auto w0op = [&](int64_t op, int rt, int q) {          // W0 [H0][IN] row tile rt, k-step q (+ b0 hi/lo columns)
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int k = 32 * q + 8 * (l >> 4) + j, o = 16 * rt + (l & 15);
-        const float bh = from_bf16(to_bf16(b0[o]));
-        const float v = k < N::IN ? w0[(int64_t)o * N::IN + k] : k == N::IN ? bh : k == N::IN + 1 ? b0[o] - bh : 0.0f;
-        put(op, l, j, v);
-      }
-  };
-  auto w1op = [&](int64_t op, int rt, int m) {          // W1 [H1][H0] row tile rt, k-step m (layer-0 group)
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) put(op, l, j, w1[(int64_t)(16 * rt + (l & 15)) * N::H0 + kperm16(m, l, j)]);
-  };
-  auto w2op = [&](int64_t op, int u) {                  // W2 [9][H1], rows padded to 16, k-step u
-    for (int l = 0; l < 64; ++l)
-      for (int j = 0; j < 8; ++j) {
-        const int o = l & 15;
-        put(op, l, j, o < N::OUT ? w2[(int64_t)o * N::H1 + kperm16(u, l, j)] : 0.0f);
-      }
-  };
-  for (int c = 0; c < N::L0C; ++c)
-    for (int mm = 0; mm < N::L0T; ++mm) {
-      const int t = c * N::L0T + mm;                     // layer-0 group
-      const int64_t base = N::chunk_off(c) + (int64_t)mm * N::U0;
-      for (int rt = 0; rt < 2; ++rt)
-        for (int q = 0; q < N::KQ0; ++q) w0op(base + rt * N::KQ0 + q, 2 * t + rt, q);
-      if (N::MODE == 1)
-        for (int v = 0; v < 2 * N::G1; ++v) w1op(base + 2 * N::KQ0 + v, v, t);
-    }
-  if (N::MODE == 0) {
-    for (int d = 0; d < N::L1C; ++d)
-      for (int uu = 0; uu < N::L1T; ++uu) {
-        const int u = d * N::L1T + uu;                   // layer-1 group
-        const int64_t base = N::chunk_off(N::L0C + d) + (int64_t)uu * N::U1;
-        for (int rt = 0; rt < 2; ++rt)
-          for (int m = 0; m < N::G0; ++m) w1op(base + rt * N::G0 + m, 2 * u + rt, m);
-        w2op(base + 2 * N::G0, u);
-      }
-  } else {
-    for (int u = 0; u < N::G1; ++u) w2op(N::chunk_off(N::L0C) + u, u);
-  }
-  float* bias = reinterpret_cast<float*>(blob.data() + N::BIAS_OFF);
-  memcpy(bias, b0, 4 * N::H0);
-  memcpy(bias + N::H0, b1, 4 * N::H1);
-  memcpy(bias + N::H0 + N::H1, b2, 4 * N::OUT);
-  return blob;
-}
-
-template <class N>
-std::vector<uint8_t> pack_f32(const float* w0, const float* b0, const float* w1, const float* b1,
-                              const float* w2, const float* b2) {
-  std::vector<uint8_t> blob(N::BYTES, 0);
-  float* f = reinterpret_cast<float*>(blob.data());
-  int64_t op = 0;
-  auto rg = [](int g) { return (g & 3) + 8 * (g >> 2); };   // accumulator register g -> row (half 0)
-  for (int p = 0; p < N::PASSES; ++p) {
-    for (int t = 0; t < N::T0; ++t) {
-      for (int q = 0; q < N::KS0P; ++q, ++op)        // W0 [H0][IN]: lane (i, h) = W0[32t + i][2q + h]
-        for (int l = 0; l < 64; ++l) {
-          const int i = l & 31, k = 2 * q + (l >> 5);
-          f[op * 64 + l] = k < N::IN ? w0[(int64_t)(32 * t + i) * N::IN + k] : 0.0f;
-        }
-      for (int g = 0; g < 16; ++g)                   // W1 [H1][H0]: k pair (r_g, r_g + 4) of tile t
-        for (int u = 0; u < N::T1P; ++u, ++op)
-          for (int l = 0; l < 64; ++l) {
-            const int i = l & 31, k = 32 * t + rg(g) + 4 * (l >> 5);
-            f[op * 64 + l] = w1[(int64_t)(32 * (p * N::T1P + u) + i) * N::H0 + k];
-          }
-    }
-    for (int u = 0; u < N::T1P; ++u)                 // W2 [9][H1], rows padded to 32 with zeros
-      for (int g = 0; g < 16; ++g, ++op)
-        for (int l = 0; l < 64; ++l) {
-          const int i = l & 31, k = 32 * (p * N::T1P + u) + rg(g) + 4 * (l >> 5);
-          f[op * 64 + l] = i < N::OUT ? w2[(int64_t)i * N::H1 + k] : 0.0f;
-        }
-  }
-  float* bias = reinterpret_cast<float*>(blob.data() + N::BIAS_OFF);
-  memcpy(bias, b0, 4 * N::H0);
-  memcpy(bias + N::H0, b1, 4 * N::H1);
-  memcpy(bias + N::H0 + N::H1, b2, 4 * N::OUT);
-  return blob;
-}
-
 struct MlpKernel {
   int in, h0, h1, precision;
   int threads, rows_per_task;
   int64_t bytes;
   void (*fwd)(MlpArgs);
   std::vector<uint8_t> (*pack)(const float*, const float*, const float*, const float*, const float*, const float*);
+  int (*pack_device)(const PackSrc&, void*, hipStream_t);
 };
 
 template <int IN, int H0, int H1, int WAVES, int MODE, int L0T, int L1T, bool XPF>
 MlpKernel make_mlp() {
   using N = Net<IN, H0, H1, WAVES, MODE, L0T, L1T, XPF>;
-  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp<N>, pack<N>};
+  using M = Map32<N>;
+  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp<N>, pack_host<N, M>, pack_device<N, M>};
 }
 
 template <int IN, int H0, int H1, int WAVES, int MODE, int L0T, int L1T, int NS = 2>
 MlpKernel make_mlp16() {
   using N = Net16<IN, H0, H1, WAVES, MODE, L0T, L1T, NS>;
-  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp16<N>, pack16<N>};
+  using M = Map16<N>;
+  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp16<N>, pack_host<N, M>, pack_device<N, M>};
 }
 
 template <int IN, int H0, int H1, int PASSES>
 MlpKernel make_mlp_f32() {
   using N = NetF<IN, H0, H1, PASSES>;
-  return MlpKernel{IN, H0, H1, WH_MLP_F32, 256, 128, N::BYTES, k_mlp_f32<N>, pack_f32<N>};
+  using M = MapF<N>;
+  return MlpKernel{IN, H0, H1, WH_MLP_F32, 256, 128, N::BYTES, k_mlp_f32<N>, pack_host<N, M>, pack_device<N, M>};
 }
 
 const MlpKernel* find_mlp(const wh_mlp_desc* d) {
@@ -1144,6 +992,14 @@ int wh_mlp_pack(const wh_mlp_desc* d, const float* w0, const float* b0, const fl
   if (!w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !packed) return WH_EINVAL;
   std::vector<uint8_t> blob = k->pack(w0, b0, w1, b1, w2, b2);
   return hip_rc(hipMemcpy(packed, blob.data(), blob.size(), hipMemcpyHostToDevice));
+}
+
+int wh_mlp_pack_device(const wh_mlp_desc* d, const float* w0, const float* b0, const float* w1,
+                       const float* b1, const float* w2, const float* b2, void* packed, void* stream) {
+  const MlpKernel* k = find_mlp(d);
+  if (!k) return d ? WH_ENOTSUP : WH_EINVAL;
+  if (!w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !packed || (uintptr_t)packed % 16 != 0) return WH_EINVAL;
+  return k->pack_device(PackSrc{w0, b0, w1, b1, w2, b2}, packed, (hipStream_t)stream);
 }
 
 static int mlp_forward(const wh_mlp_desc* d, const void* packed, int64_t rows, const float* obs,

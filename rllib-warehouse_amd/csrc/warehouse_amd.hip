@@ -39,6 +39,7 @@
 #include "abi_args.h"
 #include "geometry.h"
 #include "philox.h"
+#include "sac_formula.h"
 #include "warehouse_amd.h"
 
 namespace {
@@ -56,6 +57,7 @@ namespace {
 #include "observe.h"        // ObsSrc, stream_rows / stream_frags, the image build, k_observe
 #include "replay.h"         // k_replay_put, k_replay_gather
 #include "prio.h"           // k_prio_fill, k_prio_update, k_prio_sample
+#include "sac.h"            // k_sac_td (the row arithmetic: sac_formula.h, shared with the host engine)
 #include "sampler.h"        // FImg, SampLds, write_image, k_sampler
 #include "pack.h"           // k_pack, k_unpack
 
@@ -906,6 +908,18 @@ int wh_replay_prio_sample(const wh_replay_prio* tree, int64_t M, const uint64_t*
   PrioSampleParams a{prio_tree_of(tree, s), M, u, wh_abi::lo32(seed), wh_abi::hi32(seed), wh_abi::lo32(draw),
                      wh_abi::hi32(draw), idx_out, q_out, total_out};
   hipLaunchKernelGGL(k_prio_sample, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, a);
+  return hip_err(hipGetLastError());
+}
+
+// ---- SAC TD targets (csrc/sac.h).  abi_args.h has checked the call.
+int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void* stream) {
+  const int rc = wh_abi::sac_td_call(M, NA, a);
+  if (rc || M == 0) return rc;
+  const int32_t spw = BT / NA;   // whole samples per workgroup
+  const int64_t groups = (M + spw - 1) / spw;
+  if (groups > 0x7FFFFFFF) return WH_EINVAL;
+  const SacParams p{*a, M, NA, spw};
+  hipLaunchKernelGGL(k_sac_td, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p);
   return hip_err(hipGetLastError());
 }
 

@@ -13,10 +13,12 @@ from .variants import *  # noqa: F401,F403
 from .batched import BatchedWarehouse, EpisodeStats  # noqa: F401
 from .vector import WarehouseBaseEnv, WarehouseVectorEnv  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401
+from .sac import QNetwork, SACCritic  # noqa: F401
 
 __all__ = []
 __all__.extend(core.__all__)
 __all__.extend(variants.__all__)
-__all__ += ["BatchedWarehouse", "EpisodeStats", "WarehouseVectorEnv", "WarehouseBaseEnv", "ReplayBuffer"]
+__all__ += ["BatchedWarehouse", "EpisodeStats", "WarehouseVectorEnv", "WarehouseBaseEnv", "ReplayBuffer",
+            "SACCritic", "QNetwork"]
 
 name = "warehouse"

@@ -46,7 +46,8 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_sampler_step", "wh_sampler_step_to", "wh_sampler_rollout", "wh_vector_step_x",
            "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide",
            "wh_replay_put", "wh_replay_gather",
-           "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample")
+           "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample",
+           "wh_mlp_pack_device", "wh_sac_td")
 
 WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
 WH_PRIO_MAX = 0x7FFFFFFF       # the largest stored priority
@@ -117,6 +118,13 @@ WH_MLP_F32 = 1
 class WhMlpDesc(ctypes.Structure):
     _fields_ = [("in_dim", ctypes.c_int32), ("hidden0", ctypes.c_int32), ("hidden1", ctypes.c_int32),
                 ("out_dim", ctypes.c_int32), ("precision", ctypes.c_int32)]
+
+
+class WhSacTdArgs(ctypes.Structure):
+    _fields_ = ([(k, ctypes.c_void_p) for k in ("pi_next", "q1t_next", "q2t_next", "q1", "q2", "actions", "rewards",
+                                                 "dones", "n")] +
+                [("alpha", ctypes.c_float), ("discount", ctypes.c_float), ("mask_dones", ctypes.c_int32)] +
+                [(k, ctypes.c_void_p) for k in ("y", "td_rows", "td")])
 
 
 class WarehouseNativeError(RuntimeError):
@@ -204,6 +212,8 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     _MD = ctypes.POINTER(WhMlpDesc)
     S.wh_mlp_query.argtypes = [_MD, ctypes.POINTER(ctypes.c_int64)]
     S.wh_mlp_pack.argtypes = [_MD] + [_P] * 7
+    S.wh_mlp_pack_device.argtypes = [_MD] + [_P] * 7 + [_P]
+    S.wh_sac_td.argtypes = [_I64, _I32, ctypes.POINTER(WhSacTdArgs), _P]
     S.wh_mlp_forward.argtypes = [_MD, _P, _I64, _P, _P, _P, _I32, _U64, ctypes.c_uint32, _P]
     S.wh_mlp_forward_x.argtypes = [_MD, _P, _I64, _P, _P, _P, _I32, _U64, ctypes.c_uint32, _P]
     S.wh_check_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), _I32]

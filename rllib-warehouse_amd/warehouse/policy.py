@@ -70,6 +70,55 @@ class MLPPolicy:
             nat.check(nat.lib().wh_mlp_pack(ctypes.byref(self.desc), *args, self.packed.data_ptr()), "wh_mlp_pack")
         self._step = 0
 
+    def _shapes(self) -> Dict[str, tuple]:
+        return dict(w0=(self.hidden[0], self.in_dim), b0=(self.hidden[0],), w1=(self.hidden[1], self.hidden[0]),
+                    b1=(self.hidden[1],), w2=(NUM_ACTIONS, self.hidden[1]), b2=(NUM_ACTIONS,))
+
+    def load_weights(self, weights: Dict[str, object]) -> None:
+        """Repack this network from `weights` (keys w0 b0 w1 b1 w2 b2, nn.Linear layout).
+
+        When every value is a contiguous float32 torch tensor on `self.device`, the blob is repacked
+        by wh_mlp_pack_device on the current stream: no copy of the weights to the host and no
+        synchronisation, so a learner refreshes its rollout policy (or a Q network) between two
+        launches.  `self.weights` then becomes None: the host copy the constructor kept would be
+        stale, and fetching a fresh one would be the very sync this avoids.  (The first device
+        repack of a shape uploads a small table and must not happen inside a stream capture.)
+        Anything else -- numpy arrays, host tensors, another dtype or device -- takes the
+        constructor's host path (wh_mlp_pack, synchronous) and refreshes `self.weights`.  Shapes are
+        checked as the constructor checks them."""
+        shapes = self._shapes()
+        on_device = all(torch.is_tensor(weights[k]) and weights[k].device == self.device and
+                        weights[k].dtype == torch.float32 and weights[k].is_contiguous() for k in shapes)
+        fp = ctypes.POINTER(ctypes.c_float)
+        if on_device:
+            for k, shp in shapes.items():
+                if tuple(weights[k].shape) != shp:
+                    raise ValueError(f"{k}: expected {shp}, got {tuple(weights[k].shape)}")
+            args = [weights[k].data_ptr() for k in shapes]
+            nat.check(nat.lib().wh_mlp_pack_device(ctypes.byref(self.desc), *args, self.packed.data_ptr(),
+                                                   nat.stream_of(self.device)), "wh_mlp_pack_device")
+            self.weights = None
+            return
+        w = {k: np.ascontiguousarray(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, np.float32))
+             for k, v in weights.items()}
+        for k, shp in shapes.items():
+            if w[k].shape != shp:
+                raise ValueError(f"{k}: expected {shp}, got {w[k].shape}")
+        args = [w[k].ctypes.data_as(fp) for k in shapes]
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().wh_mlp_pack(ctypes.byref(self.desc), *args, self.packed.data_ptr()), "wh_mlp_pack")
+        self.weights = w
+
+    def copy_from(self, other: "MLPPolicy") -> None:
+        """This network's packed blob <- `other`'s, a device-to-device copy on the current stream:
+        the YAMLs' target update (tau: 1.0, every target_network_update_freq steps).  Both must have
+        the same variant shape and precision (blobs are specific to both)."""
+        same = (self.in_dim, self.hidden, self.precision) == (other.in_dim, other.hidden, other.precision)
+        if not same or self.packed.numel() != other.packed.numel():
+            raise ValueError("copy_from: the two networks differ in variant or precision")
+        self.packed.copy_(other.packed, non_blocking=True)
+        self.weights = other.weights
+
     def forward(self, obs: torch.Tensor, *, explore: bool = False, seed: int = 0, step: Optional[int] = None,
                 actions: Optional[torch.Tensor] = None, logits: Optional[torch.Tensor] = None):
         """obs [..., 9R+1] f32 device rows -> (actions [...] int32, logits [..., 9] f32 or None).
@@ -111,6 +160,22 @@ class MLPPolicy:
                                              actions.data_ptr(), int(bool(explore)), int(seed), int(step) & 0xFFFFFFFF,
                                              nat.stream_of(self.device)), "wh_mlp_forward_x")
         return actions, (logits if torch.is_tensor(logits) else None)
+
+
+def weights_of(module) -> Dict[str, torch.Tensor]:
+    """The six parameter tensors of a torch.nn.Sequential(Linear, ReLU, Linear, ReLU, Linear) under
+    the keys MLPPolicy takes, detached and without copies (they share the module's storage): what
+    `policy.load_weights(weights_of(module))` packs after an optimiser step."""
+    linears = [m for m in module if isinstance(m, torch.nn.Linear)]
+    acts = [m for m in module if not isinstance(m, torch.nn.Linear)]
+    if len(linears) != 3 or len(module) != 5 or not all(isinstance(m, torch.nn.ReLU) for m in acts) or \
+            any(m.bias is None for m in linears):
+        raise ValueError("weights_of: expected Sequential(Linear, ReLU, Linear, ReLU, Linear) with biases")
+    out = {}
+    for i, m in enumerate(linears):
+        out[f"w{i}"] = m.weight.detach()
+        out[f"b{i}"] = m.bias.detach()
+    return out
 
 
 def policy_rollout(env, net: MLPPolicy, steps: int, *, explore: bool = False, seed: int = 0,

@@ -1,0 +1,136 @@
+"""The forward half of a SAC learner on the device: Q networks, TD targets and TD errors
+(include/warehouse_amd.h, SAC TD TARGETS; csrc/sac.h).
+
+The Q_model of scripts/experiments/warehouse-{small,medium,large}-sac/*.yaml has the policy_model's
+shape (a ReLU MLP with one output per action), so a Q network is an `MLPPolicy` whose nine outputs
+are read as Q values, and it runs on the same kernels from the same operands `ReplayBuffer.sample`
+writes.  `SACCritic` holds the policy, the (twin) Q networks and their targets, and turns a sampled
+batch into RLlib's discrete-SAC TD target `y`, the per-row TD errors and one TD error per ring entry
+-- what `ReplayBuffer.update_priorities` takes -- on the current stream with no host sync:
+
+    critic = SACCritic(policy, q1, q2, q1_target, q2_target, alpha=0.2, gamma=0.99)
+    batch = buf.sample(64, fragments=True)
+    out = critic.td(batch)                              # y [M,NA], td_rows [M,NA], td [M]
+    buf.update_priorities(batch["idx_out"], out["td"])
+    policy.load_weights(weights_of(policy_module))      # after the learner's optimiser step
+    critic.sync_targets()                               # every target_network_update_freq steps
+
+Gradients, optimisers, the actor and alpha losses and soft target updates (tau < 1) are the
+learner's, in torch; it hands new parameters back with `MLPPolicy.load_weights`.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict, Optional
+
+import torch
+
+from . import _native as nat
+from .batched import _check_out
+from .policy import NUM_ACTIONS, MLPPolicy
+
+QNetwork = MLPPolicy   # the same shapes; the 9 outputs are Q(s, a) for the 9 moves
+
+
+class SACCritic:
+    def __init__(self, policy: MLPPolicy, q1: MLPPolicy, q2: Optional[MLPPolicy], q1_target: MLPPolicy,
+                 q2_target: Optional[MLPPolicy], *, alpha: float, gamma: float = 0.99, n_step: int = 1,
+                 mask_dones: bool = False):
+        """`q2` and `q2_target` may both be None (no twin Q).  `alpha` (the entropy coefficient) is
+        a plain attribute: a learner sets it from its log_alpha before a call.  `mask_dones=False`
+        is what the YAMLs train with (no_done_at_end: true): the bootstrap ignores the done flag."""
+        if (q2 is None) != (q2_target is None):
+            raise ValueError("SACCritic: q2 and q2_target come together (both, or neither)")
+        nets = [n for n in (policy, q1, q2, q1_target, q2_target) if n is not None]
+        for n in nets:
+            if not isinstance(n, MLPPolicy):
+                raise ValueError("SACCritic: the networks are MLPPolicy / QNetwork objects")
+            if (n.in_dim, n.device) != (policy.in_dim, policy.device):
+                raise ValueError("SACCritic: every network takes the policy's rows, on the policy's device")
+        self.policy, self.q1, self.q2, self.q1_target, self.q2_target = policy, q1, q2, q1_target, q2_target
+        self.device = policy.device
+        self.alpha = float(alpha)
+        self.gamma = float(gamma)
+        self.n_step = int(n_step)
+        self.mask_dones = bool(mask_dones)
+        self._buf: Dict[tuple, torch.Tensor] = {}
+
+    # ------------------------------------------------------------------ buffers
+    def _own(self, k: str, shape, dt=torch.float32) -> torch.Tensor:
+        key = (k, tuple(shape))
+        if key not in self._buf:
+            self._buf = {kk: v for kk, v in self._buf.items() if kk[0] != k}   # one size kept per key
+            self._buf[key] = torch.empty(shape, dtype=dt, device=self.device)
+        return self._buf[key]
+
+    def _forward(self, net: MLPPolicy, batch, side: str, rows: int, name: str) -> torch.Tensor:
+        """The logits of `net` on one side of the batch ("" = obs, "next_" = next_obs), into a
+        critic-owned [rows, 9] buffer: from the fragment operand when the batch has it and the
+        network is bf16, else from the f32 rows."""
+        out = self._own(name, (rows, NUM_ACTIONS))
+        scratch = self._own("actions", (rows,), torch.int32)
+        frag, obs = batch.get(side + "xfrag"), batch.get(side + "obs")
+        if frag is not None and net.precision == "bf16":
+            net.forward_x(frag, rows, logits=out, actions=scratch, step=0)
+        elif obs is not None:
+            net.forward(obs.view(rows, -1), logits=out, actions=scratch, step=0)
+        else:
+            raise ValueError(f"SACCritic: the batch holds no {side}obs rows" +
+                             (" (an f32 network reads rows: sample(rows=True))" if frag is not None else
+                              f" and no {side}xfrag operand"))
+        return out
+
+    def _run(self, batch, out, with_q: bool) -> Dict[str, torch.Tensor]:
+        for k in ("actions", "rewards"):
+            if k not in batch:
+                raise ValueError(f"SACCritic: the batch lacks {k!r}")
+        M, NA = batch["rewards"].shape
+        rows = M * NA
+        keys = ("y", "td_rows", "td") if with_q else ("y",)
+        shapes = dict(y=(M, NA), td_rows=(M, NA), td=(M,))
+        if out is None:
+            res = {k: self._own("out_" + k, shapes[k]) for k in keys}
+        else:
+            res = dict(out)
+            if not res or any(k not in keys for k in res):
+                raise ValueError(f"out: some of {keys}, got {sorted(res)}")
+            for k, v in res.items():
+                _check_out(v, shapes[k], torch.float32, self.device)
+        if self.mask_dones and "dones" not in batch:
+            raise ValueError("SACCritic: mask_dones needs the batch's dones")
+        if M == 0:
+            return res
+        pi = self._forward(self.policy, batch, "next_", rows, "pi_next")
+        q1t = self._forward(self.q1_target, batch, "next_", rows, "q1t_next")
+        q2t = self._forward(self.q2_target, batch, "next_", rows, "q2t_next") if self.q2_target is not None else None
+        q1 = self._forward(self.q1, batch, "", rows, "q1") if with_q else None
+        q2 = self._forward(self.q2, batch, "", rows, "q2") if with_q and self.q2 is not None else None
+        n, dones = batch.get("n"), batch.get("dones")
+        args = nat.WhSacTdArgs(pi.data_ptr(), q1t.data_ptr(), nat.ptr(q2t), nat.ptr(q1), nat.ptr(q2),
+                               nat.ptr(batch["actions"]), nat.ptr(batch["rewards"]), nat.ptr(dones), nat.ptr(n),
+                               self.alpha, self.gamma ** self.n_step, int(self.mask_dones),
+                               nat.ptr(res.get("y")), nat.ptr(res.get("td_rows")), nat.ptr(res.get("td")))
+        nat.check(nat.lib().wh_sac_td(M, NA, ctypes.byref(args), nat.stream_of(self.device)), "wh_sac_td")
+        return res
+
+    # ------------------------------------------------------------------ the surface
+    def td(self, batch: Dict[str, torch.Tensor], *, out: Optional[Dict[str, torch.Tensor]] = None):
+        """`batch`: a ReplayBuffer.sample(..., fragments=True) dict (bf16 networks read the xfrag /
+        next_xfrag operands), or one with rows (obs / next_obs; what f32-precision networks read).
+        Runs the policy and the target Q networks on the next side and the Q networks on the obs
+        side (five forwards, three without a twin), then wh_sac_td.  Returns {"y" [M,NA], "td_rows"
+        [M,NA], "td" [M]}: the critic's own tensors, overwritten by its next call, or the caller's
+        through `out` (any of the three keys).  td[m] is one TD error per ring entry, the mean over
+        its live agent rows: `buf.update_priorities(batch["idx_out"], out["td"])`."""
+        return self._run(batch, out, True)
+
+    def targets(self, batch: Dict[str, torch.Tensor], *, out: Optional[Dict[str, torch.Tensor]] = None):
+        """Only the three next-side forwards and {"y"}: for a learner that wants the target without
+        gradient and computes Q(obs) itself under autograd.  The same `y` as td(), bit for bit."""
+        return self._run(batch, out, False)
+
+    def sync_targets(self) -> None:
+        """q1_target <- q1 and q2_target <- q2 (MLPPolicy.copy_from): the YAMLs' hard target update."""
+        self.q1_target.copy_from(self.q1)
+        if self.q2_target is not None:
+            self.q2_target.copy_from(self.q2)

@@ -28,6 +28,27 @@ def code_object(lib, tmp):
     return co
 
 
+def code_objects(lib, tmp):
+    """Every gfx950 code object of the library: .hip_fatbin holds one offload bundle per translation
+    unit (warehouse_amd.hip, policy_mlp.hip), one after the other; code_object() sees the first."""
+    fat = os.path.join(tmp, "fatbin_all")
+    subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", lib, os.path.join(tmp, "junk")],
+                   check=True)
+    data = open(fat, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
+    out = []
+    for i, s in enumerate(starts):
+        part = os.path.join(tmp, f"bundle{i}")
+        with open(part, "wb") as fh:
+            fh.write(data[s:starts[i + 1] if i + 1 < len(starts) else len(data)])
+        co = os.path.join(tmp, f"gfx950_{i}.co")
+        subprocess.run([f"{LLVM}/clang-offload-bundler", "--type=o", f"--input={part}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}", "--unbundle"], check=True)
+        out.append(co)
+    return out
+
+
 def kernels(co):
     text = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
     out = []
@@ -57,7 +78,7 @@ def main():
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
-        ks = kernels(code_object(a.lib, tmp))
+        ks = [k for co in code_objects(a.lib, tmp) for k in kernels(co)]
     for k, d in zip(ks, demangle([k["name"] for k in ks])):
         k["demangled"] = d
     ks = [k for k in ks if a.grep in k["demangled"]]
