@@ -1,6 +1,7 @@
 // mlp_pack.h -- the packed weight blob of the policy network, written once for the host
 // (wh_mlp_pack) and the device (wh_mlp_pack_device).  Part of policy_mlp.hip's anonymous namespace;
-// needs Net / Net16 / NetF and u32x4 before it.
+// needs mlp32.h, mlp16.h and mlp_f32.h (Net / Net16 / NetF), <mutex>, <utility>, <vector> and hip_rc
+// before it.
 //
 // A blob is a stream of MFMA A operands in the order the forward kernel consumes them, then the f32
 // biases.  What differs between the three blob formats is which weight lands in element j of lane l
@@ -249,7 +250,7 @@ int pack_table(hipStream_t stream, const PackOp** out) {
   static std::vector<std::pair<int, PackOp*>> seen;
   int dev = 0;
   hipError_t he = stream ? hipStreamGetDevice(stream, &dev) : hipGetDevice(&dev);
-  if (he != hipSuccess) return WH_EHIP + (int)he;
+  if (he != hipSuccess) return hip_rc(he);
   std::lock_guard<std::mutex> lk(mu);
   for (const auto& s : seen)
     if (s.first == dev) {
@@ -260,13 +261,13 @@ int pack_table(hipStream_t stream, const PackOp** out) {
   MAP::walk([&](int64_t op, PackOp d) { tab[(size_t)op] = d; });
   int cur = 0;
   he = hipGetDevice(&cur);
-  if (he != hipSuccess) return WH_EHIP + (int)he;
-  if (cur != dev && (he = hipSetDevice(dev)) != hipSuccess) return WH_EHIP + (int)he;
+  if (he != hipSuccess) return hip_rc(he);
+  if (cur != dev && (he = hipSetDevice(dev)) != hipSuccess) return hip_rc(he);
   PackOp* d = nullptr;
   he = hipMalloc(&d, tab.size() * sizeof(PackOp));
   if (he == hipSuccess) he = hipMemcpy(d, tab.data(), tab.size() * sizeof(PackOp), hipMemcpyHostToDevice);
   if (cur != dev) (void)hipSetDevice(cur);
-  if (he != hipSuccess) return WH_EHIP + (int)he;
+  if (he != hipSuccess) return hip_rc(he);
   seen.emplace_back(dev, d);
   *out = d;
   return WH_OK;
@@ -280,6 +281,5 @@ int pack_device(const PackSrc& src, void* packed, hipStream_t stream) {
   const PackArgs a{src, table, static_cast<u32x4*>(packed)};
   constexpr int64_t PIECES = N::BYTES / 16;
   hipLaunchKernelGGL((k_mlp_pack<N, MAP>), dim3((unsigned)((PIECES + 255) / 256)), dim3(256), 0, stream, a);
-  const hipError_t he = hipGetLastError();
-  return he == hipSuccess ? WH_OK : WH_EHIP + (int)he;
+  return hip_rc(hipGetLastError());
 }

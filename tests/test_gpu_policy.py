@@ -78,6 +78,56 @@ def test_mlp_logits_and_argmax_vs_torch(wh, variant, na):
     np.testing.assert_array_equal(a2.cpu().numpy(), acts)
 
 
+@pytest.mark.parametrize("variant", ["small", "medium", "large"])
+def test_mlp_persistent_walk_equals_single_task_launches(wh, variant):
+    """One launch of more 256-row tasks than the device has CUs, so some persistent workgroups walk a
+    second task (it > 0, Small's next-task X prefetch, k_mlp16's load_x(task + gridDim.x)), against
+    the same rows launched in slices of 8,192 rows = 32 tasks, where no workgroup takes a second one.
+    Tolerance 0: a column of an MFMA tile depends only on its own B column and slice boundaries are
+    multiples of 256 rows, so every row keeps its wave, lane and summation order.  Every 97th row of
+    the big launch is also held to the file's bound against the bf16-rounding float64 reference.
+    (explore=1 is not compared: its noise is keyed by the absolute row.)"""
+    import torch
+
+    rows, slice_rows = 76_837, 8_192
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert 32 <= cus and rows > 256 * cus, cus       # the big launch walks, the slices do not
+    net = wh.policy.MLPPolicy(variant, seed=11)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    x = (torch.randn((rows, net.in_dim), generator=g) * 4).to(net.device)
+    # a fragment-order operand as tools/mlp_hash.py builds it: random bf16 of magnitude [0.5, 1) in
+    # every column, the two bias columns and the padding included
+    kq = (net.in_dim + 2 + 15) // 16
+    bits = torch.randint(0, 1 << 15, ((rows + 31) // 32, kq, 64, 8), generator=g, dtype=torch.int32).to(net.device)
+    xf = ((bits & 0x807F) | 0x3F00).to(torch.int16).view(torch.uint8).contiguous()
+
+    def sliced(launch):
+        acts, lgs = zip(*[launch(r0, min(slice_rows, rows - r0)) for r0 in range(0, rows, slice_rows)])
+        assert len(acts) == 10 and acts[-1].numel() == rows - 9 * slice_rows      # the last slice is ragged
+        return torch.cat(acts), torch.cat(lgs)
+
+    acts, lg = net(x, logits=True)
+    acts_s, lg_s = sliced(lambda r0, n: net(x[r0:r0 + n], logits=True))
+    assert torch.equal(lg, lg_s) and torch.equal(acts, acts_s)
+    acts_x, lg_x = net.forward_x(xf, rows, logits=True)
+    acts_xs, lg_xs = sliced(lambda r0, n: net.forward_x(xf[r0 // 32:(r0 + n + 31) // 32], n, logits=True))
+    assert torch.equal(lg_x, lg_xs) and torch.equal(acts_x, acts_xs)
+
+    pick = np.arange(0, rows, 97)
+    ref = reference_logits(net.weights, x.cpu().numpy()[pick], bf16=True)
+    np.testing.assert_array_less(np.abs(lg.cpu().numpy()[pick] - ref), 2e-3 + 2e-3 * np.abs(ref))
+    # the fragment operand's rows, decoded (frag_reference's layout backwards); its bias columns are
+    # random too, so the reference multiplies them with b0's bf16 hi + lo pair as the kernel does
+    fr = xf.view(torch.int16).reshape(-1, kq, 2, 32, 8).permute(0, 3, 1, 2, 4).reshape(-1, 16 * kq)[pick]
+    xd = (fr.to(torch.int32) << 16).view(torch.float32).cpu().numpy()[:, :net.in_dim + 2]
+    b0 = torch.as_tensor(net.weights["b0"])
+    hi = b0.to(torch.bfloat16).to(torch.float32)
+    w = dict(net.weights, w0=np.concatenate([net.weights["w0"], hi[:, None].numpy(), (b0 - hi)[:, None].numpy()], 1),
+             b0=np.zeros_like(net.weights["b0"]))
+    ref_x = reference_logits(w, xd, bf16=True)
+    np.testing.assert_array_less(np.abs(lg_x.cpu().numpy()[pick] - ref_x), 2e-3 + 2e-3 * np.abs(ref_x))
+
+
 def test_mlp_explore_samples_softmax(wh):
     import torch
 

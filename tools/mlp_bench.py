@@ -10,9 +10,7 @@ import warehouse.policy as wp  # noqa: E402
 
 B = int(os.environ.get("MLP_B", 65536))
 VARIANTS = os.environ.get("MLP_VARIANTS", "small,medium,large").split(",")
-for abl, variant, na in [(a, v, n) for a in os.environ.get("MLP_ABLATE", "0").split(",")
-                         for v, n in (("small", 4), ("medium", 8), ("large", 16)) if v in VARIANTS]:
-    os.environ["WH_MLP_ABLATE"] = abl
+for variant, na in [(v, n) for v, n in (("small", 4), ("medium", 8), ("large", 16)) if v in VARIANTS]:
     net = wp.MLPPolicy(variant, seed=1)
     rows = B * na
     x = torch.randn((rows, net.in_dim), device="cuda") * 4
@@ -38,7 +36,7 @@ for abl, variant, na in [(a, v, n) for a in os.environ.get("MLP_ABLATE", "0").sp
     us = t0.elapsed_time(t1) / reps * 1e3
     h0, h1 = net.hidden
     flop = 2.0 * rows * (net.in_dim * h0 + h0 * h1 + h1 * 9)
-    print(f"ablate={abl} {variant:6s} rows={rows:8d} [{net.in_dim},{h0},{h1},9] {us:9.1f} us  {flop / us / 1e6:7.1f} TFLOP/s",
+    print(f"{variant:6s} rows={rows:8d} [{net.in_dim},{h0},{h1},9] {us:9.1f} us  {flop / us / 1e6:7.1f} TFLOP/s",
           flush=True)
     if os.environ.get("MLP_LIB") == "1":
         # the same network through the vendor library (torch bf16 linear = hipBLASLt GEMMs, unfused
