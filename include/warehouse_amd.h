@@ -327,6 +327,34 @@ int wh_mlp_forward_x(const wh_mlp_desc* d, const void* packed, int64_t rows, con
                      float* logits, int32_t* actions, int32_t explore, uint64_t seed, uint32_t step,
                      void* stream);
 
+/* Several forwards of ONE network shape in one launch: up to WH_MLP_MAX_JOBS (network, input, output)
+ * jobs that share `d` run side by side, the launch's workgroups shared out among them by their row
+ * counts (csrc/mlp_grid.h).  A forward of a few hundred rows fills a few CUs; a SAC learner's three or
+ * five such forwards (policy, target Qs, Qs) then cost about one instead of running one after the other.
+ * For every job, `logits` and `actions` hold byte for byte what wh_mlp_forward (obs) or wh_mlp_forward_x
+ * (xfrag) writes for the same arguments.  One launch on `stream`; no host sync, no allocation.  A bf16
+ * job reads either `obs` or `xfrag`, each job as it likes.
+ * Checked in this order before anything is launched (a refused call launches and writes nothing):
+ * d == NULL WH_EINVAL; an unknown shape WH_ENOTSUP; njobs < 0 or > WH_MLP_MAX_JOBS, or njobs > 0 with
+ * jobs == NULL, WH_EINVAL; then per job the rules of wh_mlp_forward: rows < 0 WH_EINVAL, rows == 0 skips
+ * the job (its other fields are not looked at), packed NULL / no input / no output / both inputs
+ * WH_EINVAL, xfrag with WH_MLP_F32 or not 16-byte aligned WH_ENOTSUP; two live jobs with the same
+ * non-NULL logits or the same non-NULL actions WH_EINVAL; an f32 launch of more than 2^31 - 1 blocks
+ * (128 rows each) WH_EINVAL.  No live job: WH_OK, nothing launched.  Device only. */
+#define WH_MLP_MAX_JOBS 8
+typedef struct wh_mlp_job {
+  const void* packed;  /* this job's blob (wh_mlp_pack / wh_mlp_pack_device) */
+  int64_t rows;
+  const float* obs;    /* f32 rows, or NULL */
+  const void* xfrag;   /* fragment-order operand, or NULL (bf16 only, 16-byte aligned) */
+  float* logits;       /* [rows, 9] or NULL */
+  int32_t* actions;    /* [rows] or NULL */
+  int32_t explore;
+  uint32_t step;
+  uint64_t seed;
+} wh_mlp_job;
+int wh_mlp_forward_multi(const wh_mlp_desc* d, int32_t njobs, const wh_mlp_job* jobs, void* stream);
+
 /* REPLAY RING: off-policy transitions kept as packed states instead of observation rows (every row
  * is a function of the packed state: 265 bytes per Medium-8 transition against 5,289 as f32 rows).
  * A ring holds `capacity` slots; a slot is one time step of all B envs.  The buffers are device

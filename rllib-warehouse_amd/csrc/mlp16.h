@@ -117,8 +117,10 @@ __device__ __forceinline__ NextChunk uniform_chunk(int op0, int dst, int nops) {
                    __builtin_amdgcn_readfirstlane(nops)};
 }
 
-template <class N>
-__global__ __launch_bounds__(N::MT) void k_mlp16(MlpArgs a) {
+template <class N, class G = GridOne>
+__global__ __launch_bounds__(N::MT) void k_mlp16(typename G::Params p) {
+  const G grid(p);                      // whose workgroup this is (mlp_common.h, grid policies)
+  const MlpArgs& a = grid.job(p);
   // ONE __shared__ object (see k_mlp)
   __shared__ __attribute__((aligned(16))) u32x4 lds[N::STAGES * N::SOPS * 64 + N::H1 / 4];
   float* b1s = reinterpret_cast<float*>(lds + N::STAGES * N::SOPS * 64);
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp16(MlpArgs a) {
   const float* gb = reinterpret_cast<const float*>(static_cast<const uint8_t*>(a.packed) + N::BIAS_OFF);
   const float* b2 = gb + N::H0 + N::H1;
   const int64_t ntask = (a.rows + N::ROWS - 1) / N::ROWS;
-  const int my_tasks = (int)((ntask - blockIdx.x + gridDim.x - 1) / gridDim.x);
+  const int my_tasks = (int)((ntask - grid.bid() + grid.nblk() - 1) / grid.nblk());
 
   for (int i = tid; i < N::H1; i += N::MT) b1s[i] = gb[N::H0 + i];
   const __amdgpu_buffer_rsrc_t wr =
@@ -197,10 +199,10 @@ __global__ __launch_bounds__(N::MT) void k_mlp16(MlpArgs a) {
       }
     }
   };
-  if (my_tasks > 0) load_x(blockIdx.x);
+  if (my_tasks > 0) load_x(grid.bid());
 
   for (int it = 0; it < my_tasks; ++it) {
-    const int64_t task = blockIdx.x + (int64_t)it * gridDim.x;
+    const int64_t task = grid.bid() + (int64_t)it * grid.nblk();
     const int base = it * N::NCH;
     const bool has_next = it + 1 < my_tasks;
     NextChunk nc;                                   // of the chunk in hand
@@ -231,7 +233,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp16(MlpArgs a) {
         nc = begin_chunk(gg + 1, true);
         // the next task's X during the last chunk (X is dead once layer 0 is done; loading it for
         // the whole of layer 1 would keep its registers live beside all of layer 0's fragments)
-        if (d == N::L1C - 1 && has_next) load_x(task + gridDim.x);
+        if (d == N::L1C - 1 && has_next) load_x(task + grid.nblk());
         f32x4 acc[2][NS];
         stream_ops<N::L1OPS>(stage_of(gg), lane, [&](int i, bf16x8 af) {
           const int uu = i / N::U1, k = i % N::U1;
@@ -280,7 +282,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp16(MlpArgs a) {
       {
         const int gg = base + N::L0C;
         nc = begin_chunk(gg + 1, true);
-        if (has_next) load_x(task + gridDim.x);
+        if (has_next) load_x(task + grid.nblk());
         stream_ops<N::L1OPS, 4, 1>(stage_of(gg), lane, [&](int u, bf16x8 af) {
 #pragma unroll
           for (int s2 = 0; s2 < NS; ++s2)

@@ -66,8 +66,10 @@ __device__ __forceinline__ void stage_chunk(const u32x4* __restrict__ src, u32x4
     __builtin_amdgcn_global_load_lds(src + o * 64 + lane, dst + o * 64, 16, 0, 0);
 }
 
-template <class N>
-__global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
+template <class N, class G = GridOne>
+__global__ __launch_bounds__(N::MT) void k_mlp(typename G::Params p) {
+  const G grid(p);                      // whose workgroup this is (mlp_common.h, grid policies)
+  const MlpArgs& a = grid.job(p);
   // two weight stages + b1; A fragments are ds_read_b128 at operand*1 KiB + lane*16: conflict-free,
   // and each 1 KiB operand is read by all WAVES waves.
   // ONE __shared__ object: with a second one beside the LDS-DMA target, hipcc (ROCm 7.2) emits
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
   // Persistent: one workgroup per CU walks the ROWS-sample tasks, so the weight pipeline (and b1)
   // carry over from task to task instead of restarting behind every workgroup's prologue.
   const int64_t ntask = (a.rows + N::ROWS - 1) / N::ROWS;
-  const int my_tasks = (int)((ntask - blockIdx.x + gridDim.x - 1) / gridDim.x);
+  const int my_tasks = (int)((ntask - grid.bid() + grid.nblk() - 1) / grid.nblk());
 
   for (int i = tid; i < N::H1; i += N::MT) b1s[i] = gb[N::H0 + i];
   auto stage_of = [&](int gg) { return lds + (gg & 1) * (N::SOPS * 64); };
@@ -134,9 +136,9 @@ __global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
   bf16x8 xb[N::KQ0];
   if (my_tasks > 0) {
     if (xf) {
-      load_xf(blockIdx.x, xb);
+      load_xf(grid.bid(), xb);
     } else {
-      const int64_t row0 = (int64_t)blockIdx.x * N::ROWS + w * 32 + r;
+      const int64_t row0 = (int64_t)grid.bid() * N::ROWS + w * 32 + r;
       float xr[N::KQ0 * 8];
       load_x(row0, xr);
       cvt_x(xr, row0 < a.rows, xb);
@@ -144,7 +146,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
   }
 
   for (int it = 0; it < my_tasks; ++it) {
-    const int64_t task = blockIdx.x + (int64_t)it * gridDim.x;
+    const int64_t task = grid.bid() + (int64_t)it * grid.nblk();
     const int64_t row = task * N::ROWS + w * 32 + r;
     const bool live = row < a.rows;               // (a wave past the end still joins the barriers)
     const int base = it * N::NCH;
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
     constexpr int NS = N::L1C >= 3 ? 2 : 1;      // parts, one per chunk
     constexpr int QP = (N::KQ0 + NS - 1) / NS, PF = N::L1C - 1 - NS;  // k-steps per part, first chunk
     static_assert(N::MODE == 1 || PF >= 0, "layer-1 chunks to prefetch in");
-    const int64_t row_next = row + (int64_t)gridDim.x * N::ROWS;
+    const int64_t row_next = row + (int64_t)grid.nblk() * N::ROWS;
     const bool has_next = it + 1 < my_tasks;
 
     f32x16 lg{};
@@ -185,7 +187,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
         const int g = base + N::L0C + d;
         fetch(g + 1);
         // fragment-order X: the next task's operand straight into xb during the last chunk
-        if (xf && d == N::L1C - 1 && has_next) load_xf(task + gridDim.x, xb);
+        if (xf && d == N::L1C - 1 && has_next) load_xf(task + grid.nblk(), xb);
         float xr[QP * 8];                         // one part at a time
         if (!xf && N::XPF && d == PF && has_next) load_x(row_next, xr, 0, QP);
         if (!xf && N::XPF && NS == 2 && d == PF + 1 && has_next) load_x(row_next, xr, QP, N::KQ0);
@@ -232,7 +234,7 @@ __global__ __launch_bounds__(N::MT) void k_mlp(MlpArgs a) {
       {
         const int g = base + N::L0C;
         fetch(g + 1);
-        if (xf && has_next) load_xf(task + gridDim.x, xb);   // X is dead once layer 0 is done
+        if (xf && has_next) load_xf(task + grid.nblk(), xb);   // X is dead once layer 0 is done
         bf16x8 f0, f1;
         stream_ops<N::L1OPS>(stage_of(g), lane, [&](int i, bf16x8 af) {
           if ((i & 1) == 0) relu_to_frags(acc1[i >> 1], b1s, 32 * (i >> 1), h, f0, f1);

@@ -22,6 +22,49 @@ struct MlpArgs {
   const u32x4* xfrag;   // non-null: X already in fragment order (wh_observe_x), obs unused
 };
 
+// Grid policies: every kernel template takes one as its second parameter, and its body asks it which
+// MlpArgs the workgroup works on (job), what its block index within that job is (bid) and how many
+// blocks the job has (nblk) instead of reading blockIdx.x / gridDim.x.
+// GridOne, the default: the whole grid is one network's (wh_mlp_forward, wh_mlp_forward_x).
+struct GridOne {
+  using Params = MlpArgs;
+  __device__ __forceinline__ explicit GridOne(const MlpArgs&) {}
+  __device__ __forceinline__ const MlpArgs& job(const MlpArgs& p) const { return p; }
+  __device__ __forceinline__ unsigned bid() const { return blockIdx.x; }
+  __device__ __forceinline__ unsigned nblk() const { return gridDim.x; }
+};
+
+// GridMulti (wh_mlp_forward_multi): up to WH_MLP_MAX_JOBS jobs of one network shape side by side in
+// one grid, blocks first[j] .. first[j + 1] - 1 being job j's (mlp_grid.h).  The table travels by
+// value as the kernel argument.  The scan depends on blockIdx.x and kernel arguments only, so the job
+// is workgroup-uniform and its fields are scalar loads from the argument segment into SGPRs; the body
+// then runs as it does for one network, with a job-local block index and stride.
+struct MlpMultiArgs {
+  MlpArgs job[WH_MLP_MAX_JOBS];
+  int32_t first[WH_MLP_MAX_JOBS + 1];
+  int32_t njobs;
+};
+struct GridMulti {
+  using Params = MlpMultiArgs;
+  int j;
+  unsigned b0, b1;
+  __device__ __forceinline__ explicit GridMulti(const MlpMultiArgs& p) {
+    int jj = 0;
+#pragma unroll
+    for (int i = 1; i < WH_MLP_MAX_JOBS; ++i)
+      if (i < p.njobs && blockIdx.x >= (unsigned)p.first[i]) jj = i;
+    j = __builtin_amdgcn_readfirstlane(jj);
+    b0 = (unsigned)p.first[j];
+    b1 = (unsigned)p.first[j + 1];
+  }
+  // (by value: the job's 64 bytes are loaded into SGPRs once, as a single launch's arguments are; a
+  // reference into the table re-read fields along the body and cost k_mlp16 Medium 8 more bytes of
+  // scratch per lane than its one-network kernel has)
+  __device__ __forceinline__ MlpArgs job(const MlpMultiArgs& p) const { return p.job[j]; }
+  __device__ __forceinline__ unsigned bid() const { return blockIdx.x - b0; }
+  __device__ __forceinline__ unsigned nblk() const { return b1 - b0; }
+};
+
 // The packed weight stream of a bf16 network (Net, Net16), in 1 KiB MFMA A operands: L0C chunks of
 // L0T layer-0 units (N0 units of U0 operands), then in MODE 0 L1C chunks of L1T layer-1 units (N1
 // units of U1 operands), in MODE 1 one chunk of TAIL operands (W2); the f32 biases b0 [H0], b1 [H1],

@@ -29,8 +29,10 @@ __device__ __forceinline__ f32x16 mfma_f32(float a, float b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
 
-template <class N>
-__global__ __launch_bounds__(256) void k_mlp_f32(MlpArgs a) {
+template <class N, class G = GridOne>
+__global__ __launch_bounds__(256) void k_mlp_f32(typename G::Params p) {
+  const G grid(p);                      // whose workgroup this is (mlp_common.h, grid policies)
+  const MlpArgs& a = grid.job(p);
   __shared__ float bias[N::H0 + N::H1];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int n = lane & 31, h = lane >> 5;
@@ -38,7 +40,7 @@ __global__ __launch_bounds__(256) void k_mlp_f32(MlpArgs a) {
   const float* gb = reinterpret_cast<const float*>(static_cast<const uint8_t*>(a.packed) + N::BIAS_OFF);
   for (int i = tid; i < N::H0 + N::H1; i += 256) bias[i] = gb[i];
   __syncthreads();
-  const int64_t task = (int64_t)blockIdx.x * 4 + w;
+  const int64_t task = (int64_t)grid.bid() * 4 + w;
   const int64_t row0 = task * 32;
   if (row0 >= a.rows) return;
   const int64_t row = row0 + n;

@@ -34,6 +34,7 @@
 #include <utility>
 #include <vector>
 
+#include "mlp_grid.h"
 #include "philox.h"
 #include "warehouse_amd.h"
 
@@ -52,6 +53,7 @@ struct MlpKernel {
   int threads, rows_per_task;
   int64_t bytes;
   void (*fwd)(MlpArgs);
+  void (*fwd_multi)(MlpMultiArgs);   // the same body under GridMulti (wh_mlp_forward_multi)
   std::vector<uint8_t> (*pack)(const float*, const float*, const float*, const float*, const float*, const float*);
   int (*pack_device)(const PackSrc&, void*, hipStream_t);
 };
@@ -60,21 +62,21 @@ template <int IN, int H0, int H1, int WAVES, int MODE, int L0T, int L1T, bool XP
 MlpKernel make_mlp() {
   using N = Net<IN, H0, H1, WAVES, MODE, L0T, L1T, XPF>;
   using M = Map32<N>;
-  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp<N>, pack_host<N, M>, pack_device<N, M>};
+  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp<N>, k_mlp<N, GridMulti>, pack_host<N, M>, pack_device<N, M>};
 }
 
 template <int IN, int H0, int H1, int WAVES, int MODE, int L0T, int L1T, int NS = 2>
 MlpKernel make_mlp16() {
   using N = Net16<IN, H0, H1, WAVES, MODE, L0T, L1T, NS>;
   using M = Map16<N>;
-  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp16<N>, pack_host<N, M>, pack_device<N, M>};
+  return MlpKernel{IN, H0, H1, WH_MLP_BF16, N::MT, N::ROWS, N::BYTES, k_mlp16<N>, k_mlp16<N, GridMulti>, pack_host<N, M>, pack_device<N, M>};
 }
 
 template <int IN, int H0, int H1, int PASSES>
 MlpKernel make_mlp_f32() {
   using N = NetF<IN, H0, H1, PASSES>;
   using M = MapF<N>;
-  return MlpKernel{IN, H0, H1, WH_MLP_F32, 256, 128, N::BYTES, k_mlp_f32<N>, pack_host<N, M>, pack_device<N, M>};
+  return MlpKernel{IN, H0, H1, WH_MLP_F32, 256, 128, N::BYTES, k_mlp_f32<N>, k_mlp_f32<N, GridMulti>, pack_host<N, M>, pack_device<N, M>};
 }
 
 const MlpKernel* find_mlp(const wh_mlp_desc* d) {
@@ -144,24 +146,52 @@ int wh_mlp_pack_device(const wh_mlp_desc* d, const float* w0, const float* b0, c
   return k->pack_device(PackSrc{w0, b0, w1, b1, w2, b2}, packed, (hipStream_t)stream);
 }
 
+// The argument rules of one forward on kernel k, shared by the one-network entry points and every job
+// of wh_mlp_forward_multi.  *live = 0: nothing to do (rows == 0; the other fields are not looked at).
+static int check_forward(const MlpKernel* k, const void* packed, int64_t rows, const float* obs, const void* xfrag,
+                         const float* logits, const int32_t* actions, bool* live) {
+  *live = false;
+  if (rows < 0) return WH_EINVAL;
+  if (rows == 0) return WH_OK;
+  if (!packed || (!obs && !xfrag) || (!logits && !actions)) return WH_EINVAL;
+  if (obs && xfrag) return WH_EINVAL;
+  if (xfrag && (k->precision != WH_MLP_BF16 || (uintptr_t)xfrag % 16 != 0)) return WH_ENOTSUP;
+  *live = true;
+  return WH_OK;
+}
+
+static MlpArgs mlp_args(const void* packed, int64_t rows, const float* obs, const void* xfrag, float* logits,
+                        int32_t* actions, int32_t explore, uint64_t seed, uint32_t step) {
+  return MlpArgs{packed, rows, obs, logits, actions, explore ? 1 : 0, (uint32_t)(seed & 0xFFFFFFFFu),
+                 (uint32_t)(seed >> 32), step, static_cast<const u32x4*>(xfrag)};
+}
+
+// CUs of the current device (one persistent workgroup per CU), asked once; 0: the runtime would not say.
+// The count of the device current at the first call stays for the process: on a host with unlike
+// devices a launch on another one still computes the same results (no result depends on the grid or on
+// wh_mlp_forward_multi's partition, whose cap this is) and only balances its load for the first.
+static int device_cus() {
+  static int cus = 0;
+  if (!cus) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  }
+  return cus;
+}
+
 static int mlp_forward(const wh_mlp_desc* d, const void* packed, int64_t rows, const float* obs,
                        const void* xfrag, float* logits, int32_t* actions, int32_t explore, uint64_t seed,
                        uint32_t step, void* stream) {
   const MlpKernel* k;
   if (const int rc = lookup_mlp(d, &k)) return rc;
-  if (rows < 0) return WH_EINVAL;
-  if (rows == 0) return WH_OK;
-  if (!packed || (!obs && !xfrag) || (!logits && !actions)) return WH_EINVAL;
-  if (xfrag && (k->precision != WH_MLP_BF16 || (uintptr_t)xfrag % 16 != 0)) return WH_ENOTSUP;
-  MlpArgs a{packed, rows, obs, logits, actions, explore ? 1 : 0, (uint32_t)(seed & 0xFFFFFFFFu),
-            (uint32_t)(seed >> 32), step, static_cast<const u32x4*>(xfrag)};
-  static int cus = 0;                         // one persistent workgroup per CU
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return WH_EHIP;
-    cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
+  bool live;
+  if (const int rc = check_forward(k, packed, rows, obs, xfrag, logits, actions, &live)) return rc;
+  if (!live) return WH_OK;
+  const MlpArgs a = mlp_args(packed, rows, obs, xfrag, logits, actions, explore, seed, step);
+  const int cus = device_cus();
+  if (!cus) return WH_EHIP;
   if (k->precision == WH_MLP_F32) {         // 32 rows per wave, 4 waves per workgroup
     const int64_t ntask = (rows + 31) / 32;
     hipLaunchKernelGGL(k->fwd, dim3((unsigned)((ntask + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
@@ -184,6 +214,48 @@ int wh_mlp_forward_x(const wh_mlp_desc* d, const void* packed, int64_t rows, con
                      void* stream) {
   if (!xfrag) return WH_EINVAL;
   return mlp_forward(d, packed, rows, nullptr, xfrag, logits, actions, explore, seed, step, stream);
+}
+
+static_assert(mlp_grid::MAX_JOBS == WH_MLP_MAX_JOBS, "mlp_grid.h and the header agree on the job limit");
+
+int wh_mlp_forward_multi(const wh_mlp_desc* d, int32_t njobs, const wh_mlp_job* jobs, void* stream) {
+  const MlpKernel* k;
+  if (const int rc = lookup_mlp(d, &k)) return rc;
+  if (njobs < 0 || njobs > WH_MLP_MAX_JOBS || (njobs > 0 && !jobs)) return WH_EINVAL;
+  // every job's own rules first, for all jobs, so that a job's own defect answers before the
+  // shared-pointer rule below sees any pair (the header's order)
+  for (int i = 0; i < njobs; ++i) {
+    bool live;
+    if (const int rc = check_forward(k, jobs[i].packed, jobs[i].rows, jobs[i].obs, jobs[i].xfrag, jobs[i].logits,
+                                     jobs[i].actions, &live))
+      return rc;
+  }
+  MlpMultiArgs m{};                          // the live jobs, in order
+  int64_t work[WH_MLP_MAX_JOBS];             // per live job: tasks (persistent) or rows (f32)
+  int n = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const wh_mlp_job& j = jobs[i];
+    bool live;
+    if (const int rc = check_forward(k, j.packed, j.rows, j.obs, j.xfrag, j.logits, j.actions, &live)) return rc;
+    if (!live) continue;
+    for (int o = 0; o < n; ++o)             // two jobs writing one buffer: the result would be either's
+      if ((j.logits && j.logits == m.job[o].logits) || (j.actions && j.actions == m.job[o].actions)) return WH_EINVAL;
+    m.job[n] = mlp_args(j.packed, j.rows, j.obs, j.xfrag, j.logits, j.actions, j.explore, j.seed, j.step);
+    work[n] = k->precision == WH_MLP_F32 ? j.rows : mlp_grid::ceil_div(j.rows, k->rows_per_task);
+    ++n;
+  }
+  if (n == 0) return WH_OK;
+  m.njobs = n;
+  if (k->precision == WH_MLP_F32) {
+    if (!mlp_grid::per_tile(n, work, m.first)) return WH_EINVAL;   // (a grid past 2^31 - 1 blocks)
+    hipLaunchKernelGGL(k->fwd_multi, dim3((unsigned)m.first[n]), dim3(256), 0, (hipStream_t)stream, m);
+    return hip_rc(hipGetLastError());
+  }
+  const int cus = device_cus();
+  if (!cus) return WH_EHIP;
+  if (!mlp_grid::persistent(n, work, cus < n ? n : cus, m.first)) return WH_EINVAL;
+  hipLaunchKernelGGL(k->fwd_multi, dim3((unsigned)m.first[n]), dim3(k->threads), 0, (hipStream_t)stream, m);
+  return hip_rc(hipGetLastError());
 }
 
 }  // extern "C"

@@ -47,7 +47,7 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide",
            "wh_replay_put", "wh_replay_gather",
            "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample",
-           "wh_mlp_pack_device", "wh_sac_td")
+           "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi")
 
 WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
 WH_PRIO_MAX = 0x7FFFFFFF       # the largest stored priority
@@ -118,6 +118,15 @@ WH_MLP_F32 = 1
 class WhMlpDesc(ctypes.Structure):
     _fields_ = [("in_dim", ctypes.c_int32), ("hidden0", ctypes.c_int32), ("hidden1", ctypes.c_int32),
                 ("out_dim", ctypes.c_int32), ("precision", ctypes.c_int32)]
+
+
+WH_MLP_MAX_JOBS = 8   # jobs of one wh_mlp_forward_multi launch
+
+
+class WhMlpJob(ctypes.Structure):
+    _fields_ = [("packed", ctypes.c_void_p), ("rows", ctypes.c_int64), ("obs", ctypes.c_void_p),
+                ("xfrag", ctypes.c_void_p), ("logits", ctypes.c_void_p), ("actions", ctypes.c_void_p),
+                ("explore", ctypes.c_int32), ("step", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
 
 
 class WhSacTdArgs(ctypes.Structure):
@@ -216,6 +225,7 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_sac_td.argtypes = [_I64, _I32, ctypes.POINTER(WhSacTdArgs), _P]
     S.wh_mlp_forward.argtypes = [_MD, _P, _I64, _P, _P, _P, _I32, _U64, ctypes.c_uint32, _P]
     S.wh_mlp_forward_x.argtypes = [_MD, _P, _I64, _P, _P, _P, _I32, _U64, ctypes.c_uint32, _P]
+    S.wh_mlp_forward_multi.argtypes = [_MD, _I32, ctypes.POINTER(WhMlpJob), _P]
     S.wh_check_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), _I32]
     S.wh_rollout_prepare.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _P,
                                      ctypes.POINTER(ctypes.c_void_p)]

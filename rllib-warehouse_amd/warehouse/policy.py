@@ -162,6 +162,84 @@ class MLPPolicy:
         return actions, (logits if torch.is_tensor(logits) else None)
 
 
+MAX_JOBS = nat.WH_MLP_MAX_JOBS
+
+
+def forward_many(jobs):
+    """Several networks of one shape, precision and device in ONE launch (wh_mlp_forward_multi): the
+    workgroups of the launch are shared out among the jobs, so small forwards that would each fill a
+    few CUs one after the other run side by side.  Every job writes byte for byte what
+    `net.forward` / `net.forward_x` writes for the same arguments.
+
+    `jobs`: up to MAX_JOBS dicts with
+        net      the MLPPolicy
+        obs      [..., 9R+1] contiguous f32 device rows, or
+        xfrag    observe_x()'s fragment-order operand, with `rows` (bf16 networks only)
+        logits   an output buffer, or True for a fresh one (default: none)
+        actions  an output buffer, or True for a fresh one; when omitted, a fresh one unless logits
+                 are asked for -- then no actions are computed (NULL goes to the ABI, no scratch)
+        explore, seed, step   as forward(); step=None takes the network's own counter
+    Returns one (actions, logits) pair per job (None for an output the job did not ask for)."""
+    jobs = list(jobs)
+    if len(jobs) > MAX_JOBS:
+        raise ValueError(f"forward_many: at most {MAX_JOBS} jobs in one launch, got {len(jobs)}")
+    if not jobs:
+        return []
+    nets = []
+    for j in jobs:
+        unknown = set(j) - {"net", "obs", "xfrag", "rows", "logits", "actions", "explore", "seed", "step"}
+        if unknown:
+            raise ValueError(f"forward_many: unknown job keys {sorted(unknown)}")
+        if not isinstance(j.get("net"), MLPPolicy):
+            raise ValueError("forward_many: every job names its MLPPolicy as 'net'")
+        nets.append(j["net"])
+    n0 = nets[0]
+    for n in nets[1:]:
+        if (n.in_dim, n.hidden, n.precision) != (n0.in_dim, n0.hidden, n0.precision) or n.device != n0.device:
+            raise ValueError("forward_many: the networks of one launch share shape, precision and device")
+    table = (nat.WhMlpJob * len(jobs))()
+    results = []
+    for t, j, net in zip(table, jobs, nets):
+        obs, xfrag = j.get("obs"), j.get("xfrag")
+        if (obs is None) == (xfrag is None):
+            raise ValueError("forward_many: a job reads either 'obs' or 'xfrag'")
+        if obs is not None:
+            if obs.shape[-1] != net.in_dim or obs.dtype != torch.float32 or not obs.is_contiguous():
+                raise ValueError(f"obs must be contiguous float32 [..., {net.in_dim}]")
+            lead = tuple(obs.shape[:-1])
+            rows = int(np.prod(lead)) if lead else 1
+        else:
+            if net.precision != "bf16":
+                raise ValueError("an 'xfrag' job needs precision='bf16'")
+            if "rows" not in j:
+                raise ValueError("forward_many: an 'xfrag' job states its 'rows'")
+            rows = int(j["rows"])
+            lead = (rows,)
+        logits, actions = j.get("logits"), j.get("actions")
+        if logits is True:
+            logits = torch.empty((*lead, NUM_ACTIONS), dtype=torch.float32, device=net.device)
+        elif logits is False:
+            logits = None
+        if actions is True or (actions is None and logits is None):
+            actions = torch.empty(lead, dtype=torch.int32, device=net.device)
+        elif actions is False:
+            actions = None
+        t.packed, t.rows = net.packed.data_ptr(), rows
+        t.obs, t.xfrag = nat.ptr(obs), nat.ptr(xfrag)
+        t.logits, t.actions = nat.ptr(logits), nat.ptr(actions)
+        t.explore, t.seed = int(bool(j.get("explore", False))), int(j.get("seed", 0))
+        if j.get("step") is not None:
+            t.step = int(j["step"]) & 0xFFFFFFFF
+        results.append((actions, logits))
+    # every job is valid: only now do the networks' own counters move (a refused call leaves them alone)
+    for t, j, net in zip(table, jobs, nets):
+        if j.get("step") is None:
+            t.step, net._step = net._step & 0xFFFFFFFF, net._step + 1
+    nat.check(nat.lib().wh_mlp_forward_multi(ctypes.byref(n0.desc), len(jobs), table, nat.stream_of(n0.device)),
+              "wh_mlp_forward_multi")
+    return results
+
+
 def weights_of(module) -> Dict[str, torch.Tensor]:
     """The six parameter tensors of a torch.nn.Sequential(Linear, ReLU, Linear, ReLU, Linear) under
     the keys MLPPolicy takes, detached and without copies (they share the module's storage): what

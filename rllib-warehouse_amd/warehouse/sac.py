@@ -27,18 +27,31 @@ import torch
 
 from . import _native as nat
 from .batched import _check_out
-from .policy import NUM_ACTIONS, MLPPolicy
+from .policy import NUM_ACTIONS, MLPPolicy, forward_many
 
 QNetwork = MLPPolicy   # the same shapes; the 9 outputs are Q(s, a) for the 9 moves
+
+# fused=None takes the one-launch route up to this many agent rows (M x NA): the largest batch at which
+# it measured faster.  SACCritic.td on one MI355X, Medium-8, five bf16 networks, fused / sequential in
+# us (profiles/mlp_multi_probe.txt): 512 rows 34.7 / 139.0, 4,096 rows 37.5 / 141.9,
+# 16,384 rows 67.4 / 146.0, 32,768 rows 95.4 / 149.7, 49,152 rows 124.6 / 156.3 -- and then the five
+# networks' 1,280 tasks share the launch's 256 workgroups where a launch each has 256 of its own:
+# 65,536 rows 174.9 / 166.4, 262,144 rows 613.7 / 602.6.  Above the threshold auto runs sequentially.
+FUSED_MAX_ROWS = 49152
 
 
 class SACCritic:
     def __init__(self, policy: MLPPolicy, q1: MLPPolicy, q2: Optional[MLPPolicy], q1_target: MLPPolicy,
                  q2_target: Optional[MLPPolicy], *, alpha: float, gamma: float = 0.99, n_step: int = 1,
-                 mask_dones: bool = False):
+                 mask_dones: bool = False, fused: Optional[bool] = None):
         """`q2` and `q2_target` may both be None (no twin Q).  `alpha` (the entropy coefficient) is
         a plain attribute: a learner sets it from its log_alpha before a call.  `mask_dones=False`
-        is what the YAMLs train with (no_done_at_end: true): the bootstrap ignores the done flag."""
+        is what the YAMLs train with (no_done_at_end: true): the bootstrap ignores the done flag.
+        `fused`: True issues a call's three or five forwards as ONE launch (policy.forward_many) and
+        needs every network to have one shape and precision; False runs them one after the other;
+        None (default) takes the one launch when the networks allow it and the batch has at most
+        FUSED_MAX_ROWS agent rows.  Both routes give the same bits.  `last_fused` says which route
+        the last call took."""
         if (q2 is None) != (q2_target is None):
             raise ValueError("SACCritic: q2 and q2_target come together (both, or neither)")
         nets = [n for n in (policy, q1, q2, q1_target, q2_target) if n is not None]
@@ -54,6 +67,17 @@ class SACCritic:
         self.n_step = int(n_step)
         self.mask_dones = bool(mask_dones)
         self._buf: Dict[tuple, torch.Tensor] = {}
+        self.one_shape = all((n.hidden, n.precision) == (policy.hidden, policy.precision) for n in nets)
+        if fused and not self.one_shape:
+            raise ValueError("SACCritic: fused=True needs every network to have one shape and precision")
+        self.fused = None if fused is None else bool(fused)
+        self.last_fused: Optional[bool] = None
+
+    def use_fused(self, rows: int) -> bool:
+        """Whether a call over `rows` agent rows takes the one-launch route."""
+        if self.fused is None:
+            return self.one_shape and rows <= FUSED_MAX_ROWS
+        return self.fused
 
     # ------------------------------------------------------------------ buffers
     def _own(self, k: str, shape, dt=torch.float32) -> torch.Tensor:
@@ -80,6 +104,31 @@ class SACCritic:
                               f" and no {side}xfrag operand"))
         return out
 
+    def _forward_fused(self, batch, rows: int, with_q: bool):
+        """_forward for all of a call's networks in one launch: logits only, so no action is computed
+        (NULL goes to the ABI) and no scratch buffer is touched."""
+        plan = [(self.policy, "next_", "pi_next"), (self.q1_target, "next_", "q1t_next"),
+                (self.q2_target, "next_", "q2t_next"), (self.q1 if with_q else None, "", "q1"),
+                (self.q2 if with_q else None, "", "q2")]
+        jobs, outs = [], []
+        for net, side, name in plan:
+            if net is None:
+                outs.append(None)
+                continue
+            out = self._own(name, (rows, NUM_ACTIONS))
+            frag, obs = batch.get(side + "xfrag"), batch.get(side + "obs")
+            if frag is not None and net.precision == "bf16":
+                jobs.append(dict(net=net, xfrag=frag, rows=rows, logits=out, step=0))
+            elif obs is not None:
+                jobs.append(dict(net=net, obs=obs.view(rows, -1), logits=out, step=0))
+            else:
+                raise ValueError(f"SACCritic: the batch holds no {side}obs rows" +
+                                 (" (an f32 network reads rows: sample(rows=True))" if frag is not None else
+                                  f" and no {side}xfrag operand"))
+            outs.append(out)
+        forward_many(jobs)
+        return outs
+
     def _run(self, batch, out, with_q: bool) -> Dict[str, torch.Tensor]:
         for k in ("actions", "rewards"):
             if k not in batch:
@@ -100,11 +149,18 @@ class SACCritic:
             raise ValueError("SACCritic: mask_dones needs the batch's dones")
         if M == 0:
             return res
+        self.last_fused = self.use_fused(rows)
+        if self.last_fused:
+            pi, q1t, q2t, q1, q2 = self._forward_fused(batch, rows, with_q)
+            return self._epilogue(batch, res, M, NA, pi, q1t, q2t, q1, q2)
         pi = self._forward(self.policy, batch, "next_", rows, "pi_next")
         q1t = self._forward(self.q1_target, batch, "next_", rows, "q1t_next")
         q2t = self._forward(self.q2_target, batch, "next_", rows, "q2t_next") if self.q2_target is not None else None
         q1 = self._forward(self.q1, batch, "", rows, "q1") if with_q else None
         q2 = self._forward(self.q2, batch, "", rows, "q2") if with_q and self.q2 is not None else None
+        return self._epilogue(batch, res, M, NA, pi, q1t, q2t, q1, q2)
+
+    def _epilogue(self, batch, res, M, NA, pi, q1t, q2t, q1, q2):
         n, dones = batch.get("n"), batch.get("dones")
         args = nat.WhSacTdArgs(pi.data_ptr(), q1t.data_ptr(), nat.ptr(q2t), nat.ptr(q1), nat.ptr(q2),
                                nat.ptr(batch["actions"]), nat.ptr(batch["rewards"]), nat.ptr(dones), nat.ptr(n),

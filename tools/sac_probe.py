@@ -16,7 +16,14 @@ Every variant is warmed up; variants are interleaved per round; device times are
     (a)  wh_sac_td on five [M*8, 9] logit tensors: one launch
     (b)  the same formula as torch ops on the same tensors (the op count is printed)
     and SACCritic.td on a sampled fragment batch: the five forwards alone, the epilogue alone, and
-    the whole call; the epilogue's bytes moved against the 8 TB/s HBM figure bench.py uses
+    the whole call (the sequential route, fused=False); the epilogue's bytes moved against the 8 TB/s
+    HBM figure bench.py uses
+  one launch for the five forwards (wh_mlp_forward_multi), Medium-8, M = 64 and M = 32,768 (--fused-m
+  for other batch sizes)
+    the five forwards alone and the whole SACCritic.td, fused=True against fused=False, interleaved.
+    A library without the entry point (the parent commit's, loaded with WAREHOUSE_AMD_LIB and
+    WAREHOUSE_AMD_AB=1 for a side-by-side run) measures the sequential route alone.
+    --only fused runs just this section
 """
 import argparse
 import ctypes
@@ -151,7 +158,7 @@ def probe_td(rounds, reps):
     for _ in range(16):
         buf.step(env.policy("greedy", 0.1), observe=False)
     nets = [MLPPolicy("medium", seed=10 + i, device=DEV) for i in range(5)]
-    critic = warehouse.SACCritic(*nets, alpha=0.2, gamma=0.99)
+    critic = warehouse.SACCritic(*nets, alpha=0.2, gamma=0.99, fused=False)
     g = torch.Generator(device=DEV).manual_seed(7)
     for M in (64, 32768):
         rows = M * NA
@@ -194,16 +201,64 @@ def probe_td(rounds, reps):
             f"{moved / (med[KA] * 1e-6) / HBM_PEAK:.3f} of the 8 TB/s HBM peak")
 
 
+def probe_fused(rounds, reps, Ms):
+    NA = 8
+    env = warehouse.BatchedWarehouse("medium", 4096, NA, seed=3, device=DEV)
+    env.reset()
+    buf = warehouse.ReplayBuffer(env, 16)
+    for _ in range(16):
+        buf.step(env.policy("greedy", 0.1), observe=False)
+    nets = [MLPPolicy("medium", seed=10 + i, device=DEV) for i in range(5)]
+    have = hasattr(nat.lib(), "wh_mlp_forward_multi")
+    seq = warehouse.SACCritic(*nets, alpha=0.2, gamma=0.99, fused=False)
+    fus = warehouse.SACCritic(*nets, alpha=0.2, gamma=0.99, fused=True) if have else None
+    say("# five forwards in one launch (wh_mlp_forward_multi) against five launches, Medium-8" +
+        ("" if have else "  -- this library lacks the entry point: the sequential route alone"))
+    for M in Ms:
+        rows = M * NA
+        batch = buf.sample(M, draw=1, rows=False, fragments=True)
+
+        def fwd_seq(r):
+            for net, side, name in zip(nets, ("next_", "next_", "next_", "", ""), ("pi_next", "q1t_next", "q2t_next", "q1", "q2")):
+                seq._forward(net, batch, side, rows, name)
+
+        def fwd_fus(r):
+            fus._forward_fused(batch, rows, True)
+
+        def td_seq(r):
+            seq.td(batch)
+
+        def td_fus(r):
+            fus.td(batch)
+
+        say(f"## Medium-8, M = {M} ({rows} agent rows, {(rows + 255) // 256} tasks per network)")
+        FS, FF = "the five forwards alone, sequential (5 launches)", "the five forwards alone, fused (1 launch)"
+        TS, TF = "SACCritic.td, fused=False (6 launches)", "SACCritic.td, fused=True (2 launches)"
+        variants = [(FS, fwd_seq, time_us), (TS, td_seq, time_us)]
+        if have:
+            want = {k: v.clone() for k, v in seq.td(batch).items()}
+            got = fus.td(batch)
+            assert all(torch.equal(got[k], want[k]) for k in want), "the two routes differ"
+            variants = [(FS, fwd_seq, time_us), (FF, fwd_fus, time_us), (TS, td_seq, time_us), (TF, td_fus, time_us)]
+        med = run(variants, rounds, reps)
+        if have:
+            say(f"forwards sequential / fused = {med[FS] / med[FF]:.2f}   td sequential / fused = {med[TS] / med[TF]:.2f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--only", choices=("all", "fused"), default="all")
+    ap.add_argument("--fused-m", type=int, nargs="+", default=[64, 32768])
     a = ap.parse_args()
     assert torch.cuda.is_available(), "sac_probe measures on the MI355X: no GPU, no numbers"
     say(f"# {nat.lib().wh_version().decode()}  {torch.cuda.get_device_name(0)}")
-    probe_pack(a.rounds, a.reps)
-    probe_td(a.rounds, a.reps)
+    if a.only == "all":
+        probe_pack(a.rounds, a.reps)
+        probe_td(a.rounds, a.reps)
+    probe_fused(a.rounds, a.reps, a.fused_m)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as fh:
