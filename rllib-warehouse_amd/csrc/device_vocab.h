@@ -257,6 +257,17 @@ __device__ __forceinline__ uint32_t action_of(uint32_t d) {
 #define WH_PHASE_MARK(name) ((void)0)
 #endif
 
+// A byte read from LDS as the 32-bit value the load instruction leaves (ds_read_u8 zero-extends).
+// Opaque to LLVM: knowing the value's 8 bits it narrows the mins and the merges of the two move loops
+// that consume it to 8 / 16 bits and widens the results again, a v_and per lookup in the step loop.
+__device__ __forceinline__ uint32_t lds_byte(const uint8_t* p) {
+  uint32_t v = *p;
+#ifndef WH_NO_BYTE_OPAQUE   // (A/B: the byte as LLVM types it)
+  asm("" : "+v"(v));
+#endif
+  return v;
+}
+
 template <class C>
 struct Regs {
   uint32_t hdr, epi;
@@ -285,9 +296,9 @@ struct Lds {
     if constexpr (cell_skew(C::D)) {
       // one v_dot4_u32_u8 of the agent word's bytes [x, dx, y, dy] with [4, 0, 132, 0]
       const uint32_t i = __builtin_amdgcn_udot4(xy16, 0x00840004u, 0u, false);
-      return reinterpret_cast<const uint8_t*>(tbl)[i];
+      return lds_byte(reinterpret_cast<const uint8_t*>(tbl) + i);
     } else {
-      return reinterpret_cast<const uint8_t*>(tbl)[__builtin_amdgcn_perm(xy16, xy16, 0x0C0C0200u)];
+      return lds_byte(reinterpret_cast<const uint8_t*>(tbl) + __builtin_amdgcn_perm(xy16, xy16, 0x0C0C0200u));
     }
   }
 
@@ -314,6 +325,7 @@ struct Lds {
   __device__ __forceinline__ uint8_t* row_byte(uint32_t cv, int tid) {
     return reinterpret_cast<uint8_t*>(this) + (pkp_offset() - ROWB) + cv * ROWB + PKW * tid;
   }
+  __device__ __forceinline__ uint32_t row_target(uint32_t cv, int tid) const { return lds_byte(row_byte(cv, tid)); }
   // Delivery cell of a target byte (target + 1; 0 reads the word before the table: never used) in
   // agent-word form: x << 8 | y << 24 in the target bytes, ones in the position bytes, so a pickup
   // is one AND of the (idle: 0xFF target bytes) agent word.
@@ -448,7 +460,15 @@ __device__ __forceinline__ void load_env_finish(Regs<C>& s, Lds<C>& L, const Raw
 #pragma unroll
   for (int w = 0; w < C::PW; ++w)
     early |= nz_hi(r.pt[w]) & swar_lt(swar_sub(r.pm[w], (t0 & 0xFFu) * 0x01010101u), thr * 0x01010101u);
+  // (LLVM folds this select of two uniform values into every step's expiry test, `any early || t >= W`,
+  // five instructions there.  -DWH_WSKIP_SCALAR pins it in a scalar register through v_readfirstlane,
+  // which leaves one compare in the step -- and measured slower: Medium-8 +0.8 %, Large-16 +5 % per
+  // 200-step launch, profiles/fused_constants_ab.txt)
+#ifdef WH_WSKIP_SCALAR
+  s.wskip = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__any(early != 0u) ? 0u : W));
+#else
   s.wskip = __any(early != 0u) ? 0u : W;
+#endif
 }
 
 template <class C>

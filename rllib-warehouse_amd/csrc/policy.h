@@ -9,12 +9,14 @@
 // reference's reset observation sends the greedy solver (availability 0, core.py:233-236).
 // Reads only the request mask and the fresh bit, so the fused step loop can run it for step t + 1
 // as soon as step t's regeneration is done (run_steps_fast, kWalkRotate).
-template <class C>
+// STEPPED: the state comes straight out of a step, which clears the fresh bit, so the mask is used as
+// it is (the bitop3 selects are opaque to LLVM: it cannot fold them on the constant).
+template <class C, bool STEPPED = false>
 __device__ __forceinline__ void policy_walk(const Regs<C>& s, const Lds<C>& L, uint32_t (&rp)[C::R],
                                             uint32_t (&tg)[C::R]) {
   const uint32_t mf = 0u - ((s.hdr >> 24) & 1u);
-  uint32_t mlo = bop3<~TA & TB>(mf, (uint32_t)s.am, 0u);
-  uint32_t mhi = bop3<~TA & TB>(mf, (uint32_t)(s.am >> 32), 0u);
+  uint32_t mlo = STEPPED ? (uint32_t)s.am : bop3<~TA & TB>(mf, (uint32_t)s.am, 0u);
+  uint32_t mhi = STEPPED ? (uint32_t)(s.am >> 32) : bop3<~TA & TB>(mf, (uint32_t)(s.am >> 32), 0u);
 #pragma unroll
   for (int r = 0; r < C::R; ++r) {
     uint32_t flo, fhi;
@@ -41,7 +43,9 @@ __device__ __forceinline__ void policy_walk(const Regs<C>& s, const Lds<C>& L, u
 // so a step loop can add them without the clamp (step_env<CLAMP = false>); wh_policy reports the
 // drawn action itself (EFF = false), as solvers.py:44-45 returns action_space.sample().
 // WALKED: rp[] / tg[] hold the state's request walk already (policy_walk); else it is done here.
-template <class C, int POLICY, bool EFF = false, bool WALKED = false>
+// EPS = false: the caller's p is 0 (the fused greedy rollout's eps = 0 instance): no random moves, and
+// neither their code nor the test of p in the step loop.
+template <class C, int POLICY, bool EFF = false, bool WALKED = false, bool EPS = true>
 __device__ __forceinline__ void policy_steps(const Regs<C>& s, const Lds<C>& L, const Keys& k,
                                              uint32_t gid, float p, uint32_t (&d)[C::NAM],
                                              uint32_t (*walk_rp)[C::R] = nullptr,
@@ -85,7 +89,7 @@ __device__ __forceinline__ void policy_steps(const Regs<C>& s, const Lds<C>& L, 
       // goal is a grid cell, so pos + d stays on the grid: step_env<CLAMP = false> adds it as is
       d[i] = pk_min_i16(pk_max_i16(pk_sub_i16(goal, pos), 0xFFFFFFFFu), 0x00010001u);
     }
-    if (WH_RARE(p > 0.0f)) {
+    if (EPS && WH_RARE(p > 0.0f)) {
 #pragma unroll
       for (int b = 0; b < (C::NAM + 1) / 2; ++b) {
         const uint4 blk = stream_block(k, gid, s.epi, t, PUR_POLICY, (uint32_t)b);

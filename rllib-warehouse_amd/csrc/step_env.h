@@ -9,9 +9,27 @@
 // always draw from philox): less code in the step loop and no per-step test of `regen`.
 // CLAMP = false: the steps come from the greedy policy, whose goals are grid cells, so pos + d
 // never leaves the grid and the off-grid rule (a clamp) is the identity.
+// rebuild and shared are wave-uniform (set from ballots, outside per-lane branches), so they live in
+// scalar registers and the per-step tests of them are scalar compares: as per-lane flags each cost a
+// v_cmp per step, and `rebuild` a register copy on the back-edge.
 struct LazyGrid {
-  bool rebuild;   // the occupancy grid may lack an agent's cell: rebuild it before the next move
-  uint32_t cm;    // slots sharing a cell (found by the last rebuild or reset): rebuild once one moves
+  bool rebuild;   // some lane's occupancy grid may lack an agent's cell: rebuild before the next move
+  uint32_t cm;    // slots sharing a cell (found by the last rebuild): rebuild once one moves
+  bool shared;    // some lane of the wave has such slots (cm != 0)
+};
+
+// What a launch's steps read of the env that only a reset changes, computed once and carried across
+// the step loop's back-edge in registers (run_steps_fast; recomputed where a reset replaced n).
+template <class C>
+struct EnvConst {
+  uint32_t live31[C::NAM];   // bit 31: slot i is live (i < n)
+  uint32_t n16;              // n << 16, the header's agent-count field
+  __device__ __forceinline__ void set(uint32_t hdr) {
+    const uint32_t n = (hdr >> 16) & 0xFFu;
+#pragma unroll
+    for (int i = 0; i < C::NAM; ++i) live31[i] = (uint32_t)i - n;
+    n16 = n << 16;
+  }
 };
 
 #ifdef WH_COUNT_REV
@@ -39,7 +57,8 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
                                          uint32_t gid, int64_t e, int na, int phase, uint32_t T,
                                          uint32_t W, float (&rew)[C::NAM], int32_t* n_inactive,
                                          int tid, int ablate, LazyGrid* lg = nullptr,
-                                         const uint4* pre_rblk = nullptr) {
+                                         const uint4* pre_rblk = nullptr,
+                                         const EnvConst<C>* ec = nullptr) {
   const uint32_t n = (s.hdr >> 16) & 0xFFu;
   uint32_t t = s.hdr & 0xFFFFu;
   uint32_t rewm[C::NAM];   // reward masks: all-ones = 1.0f
@@ -159,7 +178,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
           const uint32_t mlive = sgn((uint32_t)i - n);
           atomicOr(&L.occ[p >> 16][tid], bop3<TA & TB>(mlive, 1u << (p & 31u), 0u));
         }
-      } else if (WH_RARE(__any(lg->rebuild))) {
+      } else if (WH_RARE(lg->rebuild)) {
         // (the terms are written so that none is shared with the move loop below: a shared one
         // would be hoisted above the branch, and the skip path would pay a register copy per term)
         const uint32_t livebits = (2u << (n - 1u)) - 1u;   // n >= 1
@@ -188,6 +207,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 #pragma unroll
         for (int i = 0; i < C::NAM; ++i) cm |= (m[i] == 0u ? 1u : 0u) << i;
         lg->cm = cm;
+        lg->shared = __any(cm != 0u);
         lg->rebuild = false;
       }
       if (ORDERED) {   // drop-in single env / BaseEnv: entries in action-dict order, records in LDS
@@ -316,7 +336,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 #pragma unroll
             for (int j = 0; j < sidx; ++j) f = min(f, (kpr ^ sk[j]) - 1u);
             f -= 0xFFFEu;   // bit 31 of f - 1 below: blocked (f was < 0xFFFF)
-            const uint32_t live31 = (uint32_t)sidx - n;                 // bit 31: sidx < n
+            const uint32_t live31 = ec ? ec->live31[sidx] : (uint32_t)sidx - n;   // bit 31: sidx < n
             const uint32_t mok = sgn(bop3<TA & ~TB & ~TC>(live31, occ31, f - 1u));
             atomicAnd(occ_at(p), bop3<~(TA & TB)>(mok, 1u << (p & 31u), 0u));
             atomicOr(occ_at(c), bop3<TA & TB>(mok, 1u << (c & 31u), 0u));
@@ -336,7 +356,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
             mokh[sidx] = mok;
             constexpr int PD = kPickDist;
             cp[sidx] = L.cell_row(moved);
-            if (sidx >= PD) tb[sidx - PD] = *L.row_byte(cp[sidx >= PD ? sidx - PD : 0], tid);
+            if (sidx >= PD) tb[sidx - PD] = L.row_target(cp[sidx >= PD ? sidx - PD : 0], tid);
             if (sidx >= 2 * PD) dst[sidx - 2 * PD] = L.dst_tb(tb[sidx >= 2 * PD ? sidx - 2 * PD : 0]);
             if (!(ablate & 8) && sidx >= 3 * PD) {
               const int j = sidx >= 3 * PD ? sidx - 3 * PD : 0;
@@ -351,7 +371,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 #pragma unroll
           for (int i = 0; i < C::NAM; ++i)
             acc |= (s.ag[i] ^ pp[i]) & (XY16 & (uint32_t)__builtin_amdgcn_sbfe((int)lg->cm, (uint32_t)i, 1u));
-          lg->rebuild = lg->rebuild || acc != 0u;
+          lg->rebuild = lg->rebuild || __any(acc != 0u);
         };
         // Where the reverse-key loop runs exactly for the waves with shared cells, that test is made
         // on its (rare) side of the branch, so the common path has no branch between the pickup
@@ -365,7 +385,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         // loop for waves without any (every key flipped).  The lazy grid knows the lanes with shared
         // cells (lg->cm, from the last rebuild; new sharing needs an existing one).  From
         // kRevSplitMaxNam agents on a single (exact) loop.
-        if (!LAZY || C::NAM > kRevSplitMaxNam || WH_RARE(__any(lg->cm != 0u))) {
+        if (!LAZY || C::NAM > kRevSplitMaxNam || WH_RARE(lg->shared)) {
 #ifdef WH_COUNT_REV   // A/B builds: count the wave-steps that take the reverse-key loop (wh_check_read)
           if (LAZY && __lane_id() == 0) atomicAdd(&g_wh_revcount[0], 1ull);
 #endif
@@ -380,7 +400,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         // the lookups and decisions the loop's last turns did not reach, in dependency order
         constexpr int PD = kPickDist;
 #pragma unroll
-        for (int i = (C::NAM > PD ? C::NAM - PD : 0); i < C::NAM; ++i) tb[i] = *L.row_byte(cp[i], tid);
+        for (int i = (C::NAM > PD ? C::NAM - PD : 0); i < C::NAM; ++i) tb[i] = L.row_target(cp[i], tid);
 #pragma unroll
         for (int i = (C::NAM > 2 * PD ? C::NAM - 2 * PD : 0); i < C::NAM; ++i) dst[i] = L.dst_tb(tb[i]);
         if (!(ablate & 8)) {
@@ -389,7 +409,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         }
         looked = true;
         if constexpr (LAZY && !CM_IN_REV) {
-          if (WH_RARE(__any(lg->cm != 0u))) shared_moved();
+          if (WH_RARE(lg->shared)) shared_moved();
         }
       }
     }
@@ -402,7 +422,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 #pragma unroll
         for (int i = 0; i < C::NAM; ++i) cp[i] = L.cell_row(s.ag[i]);
 #pragma unroll
-        for (int i = 0; i < C::NAM; ++i) tb[i] = *L.row_byte(cp[i], tid);
+        for (int i = 0; i < C::NAM; ++i) tb[i] = L.row_target(cp[i], tid);
 #pragma unroll
         for (int i = 0; i < C::NAM; ++i) dst[i] = L.dst_tb(tb[i]);
 #pragma unroll
@@ -522,7 +542,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
     for (int i = 0; i < C::NAM; ++i) rew[i] = __uint_as_float(bop3<(TA | TB) & TC>(rewm[i], delm[i], 0x3F800000u));
     WH_PHASE_MARK(tail);
     done = t >= T;                                            // core.py:438
-    s.hdr = t | (n << 16);                                    // clears `fresh`
+    s.hdr = t | (ec ? ec->n16 : n << 16);                     // clears `fresh`
   }
   return done;
 }

@@ -124,7 +124,7 @@ struct FastRun {
   LazyGrid lg;
   uint32_t act[POLICY == POL_EXTERNAL ? C::NAM : 1];   // external actions of the (single) step
   __device__ __forceinline__ FastRun(const StepParams& a, int64_t e)
-      : rrow(a.rewards + e * C::NAM), drow(a.dones + e), rstride(a.B * C::NAM), lg{true, 0u} {}   // the grid starts empty (k_step)
+      : rrow(a.rewards + e * C::NAM), drow(a.dones + e), rstride(a.B * C::NAM), lg{true, 0u, false} {}   // the grid starts empty (k_step)
   // POL_EXTERNAL: the step's actions, loaded with the state in the prologue (their HBM latency then
   // overlaps the table loads instead of sitting on the first step)
   __device__ __forceinline__ void load_actions(const StepParams& a, int64_t e) {
@@ -173,6 +173,9 @@ struct FastRun {
       // a few envs of a full wave end (desynchronised episodes): wave-wide resets of them, one env
       // at a time (every lane takes part, so not in a tail wave whose lanes past B have exited)
       const bool full = __ballot(true) == ~0ull;
+      // every form below clears grid columns of the lanes it resets; the flag is the wave's (LazyGrid),
+      // so it is set here, outside the per-lane branches
+      lg.rebuild = true;
       if (SLOTS && a.steps >= kSlotMinSteps && __popcll(dm) <= kSlotResetMax && full) {
         // their precomputed next-episode states, after (re)filling the wave's slots if one of
         // theirs is stale: one wave-wide fill (every lane's next episode) serves the resets of
@@ -181,21 +184,17 @@ struct FastRun {
           if (__any(done && RS->rs_ep[tid] != s.epi + 1u))
             reset_philox<C, C::NAM, true>(s, L, k, gid, C::NAM, a.variable_n, (uint32_t)a.W, tid, RS);
           for (uint64_t m = dm; m; m &= m - 1ull) reset_from_slot<C, C::NAM>(s, L, *RS, (uint32_t)a.W, tid, __builtin_ctzll(m));
-          lg.rebuild = lg.rebuild || done;   // their grid columns were cleared
         }
       } else if (__popcll(dm) == 1 && full) {
         // short launches (the sampler's 1-step ones): a fill would serve few later resets
         reset_lane<C, C::NAM>(s, L, k, gid, a.variable_n, (uint32_t)a.W, tid, __builtin_ctzll(dm));
-        lg.rebuild = lg.rebuild || done;   // its grid column was cleared
       } else if (dm == ~0ull) {
         // every lane of the wave (synchronised episodes): the grid and pickup plane cleared wave-wide
         reset_philox<C, C::NAM, false, true>(s, L, k, gid, C::NAM, a.variable_n, (uint32_t)a.W, tid);
-        lg.rebuild = true;
       } else if (done) {
         reset_philox<C, C::NAM>(s, L, k, gid, C::NAM, a.variable_n, (uint32_t)a.W, tid);
 #pragma unroll
         for (int y = 0; y < C::D; ++y) L.occ[y][tid] = 0u;
-        lg.rebuild = true;
       }
     }
     WH_CHECK_ENV(s, L, e, tid);
@@ -204,7 +203,9 @@ struct FastRun {
 
 // k_step's fused rollout loop: FastRun's step, written out as one loop (the same body as a member
 // call measured 2 % slower per step at Medium-8: profiles/r04_fastrun_ab.txt).
-template <class C, int POLICY, bool SLOTS = true>
+// EPS = false: the launch's exploration rate is 0 (resolve_step), so the greedy policy's random-move
+// block and its per-step test of the rate are compiled out.
+template <class C, int POLICY, bool SLOTS = true, bool EPS = true>
 __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, Lds<C>& L, Slots<C>* RS,
                                                const Keys& k, uint32_t gid, int64_t e, int tid) {
   const int ablate = WH_ABLATE_WORD(a);
@@ -212,7 +213,9 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
   float* rrow = a.rewards + (e - tid) * C::NAM;
   uint8_t* drow = a.dones + (e - tid);
   const int64_t rstride = a.B * C::NAM;
-  LazyGrid lg{true, 0u};   // the grid starts empty (k_step)
+  LazyGrid lg{true, 0u, false};   // the grid starts empty (k_step)
+  EnvConst<C> ec;   // n changes only in a reset
+  ec.set(s.hdr);
   // ROT: the step's request walk was made at the end of the previous step (kWalkRotate); the first
   // step's here, and a reset's -- which replaces the request mask and sets `fresh` -- after it
   constexpr bool ROT = kWalkRotate && POLICY == POL_GREEDY && !kAblationBuild;
@@ -226,9 +229,9 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
     } else if (ablate & 1) {
       ablation_moves<C>(L, stp, d);
     } else if constexpr (ROT) {
-      policy_steps<C, POLICY, true, true>(s, L, k, gid, a.p, d, &wrp, &wtg);
+      policy_steps<C, POLICY, true, true, EPS>(s, L, k, gid, a.p, d, &wrp, &wtg);
     } else {
-      policy_steps<C, POLICY, POLICY == POL_GREEDY && !kAblationBuild>(s, L, k, gid, a.p, d);
+      policy_steps<C, POLICY, POLICY == POL_GREEDY && !kAblationBuild, false, EPS>(s, L, k, gid, a.p, d);
     }
     // The regeneration almost always draws (some lane of the wave reopens a point on nearly every
     // step), so its first Philox block -- a chain of ten dependent rounds -- is computed here, where
@@ -239,8 +242,12 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
     float rew[C::NAM];
     const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, true>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
                                                 (uint32_t)a.T, (uint32_t)a.W, rew, nullptr, tid, ablate, &lg,
+#ifndef WH_NO_ENV_CONST   // (A/B: n and the live masks recomputed from the header in every step)
+                                                &rb, &ec);
+#else
                                                 &rb);
-    if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);   // the next step's (redone below after a reset)
+#endif
+    if constexpr (ROT) policy_walk<C, true>(s, L, wrp, wtg);   // the next step's (redone below after a reset)
     if (!(ablate & 64)) {
       store_row<C>(rrow + tid * C::NAM, rew);
       drow[tid] = done ? 1 : 0;
@@ -252,6 +259,9 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
       // a few envs of a full wave end (desynchronised episodes): wave-wide resets of them, one env
       // at a time (every lane takes part, so not in a tail wave whose lanes past B have exited)
       const bool full = __ballot(true) == ~0ull;
+      // every form below clears grid columns of the lanes it resets; the flag is the wave's (LazyGrid),
+      // so it is set here, outside the per-lane branches
+      lg.rebuild = true;
       if (SLOTS && a.steps >= kSlotMinSteps && __popcll(dm) <= kSlotResetMax && full) {
         // their precomputed next-episode states, after (re)filling the wave's slots if one of
         // theirs is stale: one wave-wide fill (every lane's next episode) serves the resets of
@@ -260,23 +270,20 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
           if (__any(done && RS->rs_ep[tid] != s.epi + 1u))
             reset_philox<C, C::NAM, true>(s, L, k, gid, C::NAM, a.variable_n, (uint32_t)a.W, tid, RS);
           for (uint64_t m = dm; m; m &= m - 1ull) reset_from_slot<C, C::NAM>(s, L, *RS, (uint32_t)a.W, tid, __builtin_ctzll(m));
-          lg.rebuild = lg.rebuild || done;   // their grid columns were cleared
         }
       } else if (__popcll(dm) == 1 && full) {
         // short launches (the sampler's 1-step ones): a fill would serve few later resets
         reset_lane<C, C::NAM>(s, L, k, gid, a.variable_n, (uint32_t)a.W, tid, __builtin_ctzll(dm));
-        lg.rebuild = lg.rebuild || done;   // its grid column was cleared
       } else if (dm == ~0ull) {
         // every lane of the wave (synchronised episodes): the grid and pickup plane cleared wave-wide
         reset_philox<C, C::NAM, false, true>(s, L, k, gid, C::NAM, a.variable_n, (uint32_t)a.W, tid);
-        lg.rebuild = true;
       } else if (done) {
         reset_philox<C, C::NAM>(s, L, k, gid, C::NAM, a.variable_n, (uint32_t)a.W, tid);
 #pragma unroll
         for (int y = 0; y < C::D; ++y) L.occ[y][tid] = 0u;
-        lg.rebuild = true;
       }
       if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);   // of the states the resets left
+      ec.set(s.hdr);
     }
     WH_CHECK_ENV(s, L, e, tid);
   }
@@ -299,8 +306,9 @@ __device__ unsigned long long g_wh_times[kTimeWaves * kTimeSlots];
 #define WH_T(i) ((void)0)
 #endif
 
-template <class C, int POLICY, bool ORDERED, bool FAST>
+template <class C, int POLICY, bool ORDERED, bool FAST, bool EPS = true>
 __global__ __launch_bounds__(BT) void k_step(StepParams a) {
+  static_assert(EPS || (FAST && POLICY == POL_GREEDY), "the eps = 0 form exists for the fused greedy rollout only");
   __shared__ Lds<C> L;
   __shared__ std::conditional_t<FAST, Slots<C>, NoSlots> RS;   // reset slots: fused rollout only
   __shared__ std::conditional_t<ORDERED, OKeys<C>, NoSlots> OK;   // dict-order move keys: ORDERED only
@@ -352,7 +360,7 @@ __global__ __launch_bounds__(BT) void k_step(StepParams a) {
   }
 
   if constexpr (FAST)
-    run_steps_fast<C, POLICY>(a, s, L, &RS, k, gid, e, tid);
+    run_steps_fast<C, POLICY, true, EPS>(a, s, L, &RS, k, gid, e, tid);
   else if (!ORDERED && a.phase == PH_ALL)
     run_steps<C, POLICY, ORDERED, PH_ALL>(a, s, L, k, gid, e, tid);
   else if constexpr (ORDERED)

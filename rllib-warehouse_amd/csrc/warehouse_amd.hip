@@ -167,6 +167,7 @@ struct Kernels {
   int D, R, NR, NAM;
   void (*step[3])(StepParams);
   void (*step_fast[3])(StepParams);   // [policy]: greedy / random fused rollouts (NAM even), else null
+  void (*step_fast_eps0)(StepParams);   // the greedy one for launches with p = 0: no random-move code
   void (*step_ordered)(StepParams);
   void (*step_wide[3])(StepParams);   // [policy]: 16 lanes per env (k_step_wide)
   void (*sampler[3])(StepParams, float*);   // [policy]: fused step + rows (k_sampler), NAM even, else null
@@ -196,6 +197,7 @@ Kernels make_kernels() {
   k.step[1] = k_step<C, POL_GREEDY, false, false>;
   k.step[2] = k_step<C, POL_RANDOM, false, false>;
   k.step_fast[0] = nullptr;   // (set below for even agent counts: wh_vector_step's common case)
+  k.step_fast_eps0 = nullptr;
   k.sampler[0] = k.sampler[1] = k.sampler[2] = nullptr;
   k.sampler_multi[0] = k.sampler_multi[1] = k.sampler_multi[2] = nullptr;
   // the multi-step sampler holds the step's LDS, its reset slots and two image buffers
@@ -204,6 +206,7 @@ Kernels make_kernels() {
     k.step_fast[0] = k_step<C, POL_EXTERNAL, false, true>;
     k.step_fast[1] = k_step<C, POL_GREEDY, false, true>;
     k.step_fast[2] = k_step<C, POL_RANDOM, false, true>;
+    k.step_fast_eps0 = k_step<C, POL_GREEDY, false, true, false>;
     if constexpr (kSamplerBuilt<C>) {
       k.sampler[0] = k_sampler<C, POL_EXTERNAL, false, true>;
       k.sampler[1] = k_sampler<C, POL_GREEDY, false, true>;
@@ -495,7 +498,11 @@ static int resolve_step(const StepCall& c, void* stream, wh_launch* out) {
   if (k->step_fast[policy] && a.phase == PH_ALL && a.rewards && a.dones && !a.returns &&
       !a.stats.episode_return && !a.mask && !a.order && !a.regen && !a.n_inactive && a.autoreset &&
       c.g.NA == k->NAM && ((uintptr_t)a.rewards & ralign) == 0)
+#ifndef WH_NO_EPS0   // (A/B: the instance that tests p in every step for every launch)
+    kern = (policy == POL_GREEDY && !(a.p > 0.0f)) ? k->step_fast_eps0 : k->step_fast[policy];   // (the kernel's own test of p)
+#else
     kern = k->step_fast[policy];
+#endif
   const bool wide = c.lanes == WH_WIDE_LANES;   // k_step_wide (csrc/step_wide.h): 16 lanes per env
   out->kern = wide ? k->step_wide[policy] : kern;
   out->grid = wide ? grid_wide(c.B) : grid_for(c.B);
@@ -503,6 +510,12 @@ static int resolve_step(const StepCall& c, void* stream, wh_launch* out) {
   out->a = a;
   out->g = c.g;
   return WH_OK;
+}
+
+// Did the step resolve to the fused rollout's fast instance of `policy` (either greedy form)?  The
+// k_sampler instances run the same step, so the sampler routes fuse the rows exactly then.
+static bool fast_step(const wh_launch& l, int policy) {
+  return l.kern == l.k->step_fast[policy] || (policy == POL_GREEDY && l.k->step_fast_eps0 && l.kern == l.k->step_fast_eps0);
 }
 
 static int enqueue(const wh_launch& l) {
@@ -604,7 +617,7 @@ static int sampler_step(const StepCall& c, void* stream) {
   wh_launch l;
   int rc = resolve_step(c, stream, &l);
   if (rc || c.B == 0) return rc;
-  if (l.kern == l.k->step_fast[c.policy] && rows_fusable(l, l.k->sampler[c.policy], c.obs))
+  if (fast_step(l, c.policy) && rows_fusable(l, l.k->sampler[c.policy], c.obs))
     return enqueue_fused(l, l.k->sampler[c.policy], c.obs);
   rc = enqueue(l);
   if (rc || !c.obs) return rc;
@@ -742,7 +755,7 @@ int wh_sampler_rollout(const wh_config* cfg, int64_t B, uint32_t* state, int32_t
   rc = resolve_step(c, stream, &l);
   if (rc || B == 0 || steps == 0) return rc;
   void (*fk)(StepParams, float*) = steps == 1 ? l.k->sampler[policy] : l.k->sampler_multi[policy];
-  if (l.kern == l.k->step_fast[policy] && rows_fusable(l, fk, obs)) return enqueue_fused(l, fk, obs);
+  if (fast_step(l, policy) && rows_fusable(l, fk, obs)) return enqueue_fused(l, fk, obs);
   // otherwise: the same steps one launch (pair) at a time
   c.steps = 1;
   for (int32_t t = 0; t < steps && rc == WH_OK; ++t) {
