@@ -143,6 +143,7 @@ int wh_observe(const wh_config* cfg, int64_t B, const uint32_t* state, float* ob
  * is supported; xfrag must be 16-byte aligned. */
 int wh_observe_x(const wh_config* cfg, int64_t B, const uint32_t* state, float* obs, void* xfrag, void* stream);
 
+#define WH_POLICY_EXTERNAL 0  /* the caller's actions (wh_replay_record) */
 #define WH_POLICY_GREEDY 1    /* baseline/solvers.py:27-58 with random_action_prob p */
 #define WH_POLICY_RANDOM 2    /* uniform over the 9 moves (action_space.sample()) */
 
@@ -382,6 +383,24 @@ typedef struct wh_replay_ring {
 int wh_replay_put(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, int64_t slot, int32_t stage,
                   const uint32_t* state, const int32_t* actions, const float* rewards, const uint8_t* dones,
                   void* stream);
+
+/* `steps` recorded steps in one launch, step k into slot (slot + k) % capacity: the same ring bytes,
+ * live state, rewards, dones, episode metrics and philox draws as, `steps` times,
+ *   [wh_policy ->] wh_replay_put(stage 0) -> wh_vector_step(autoreset = 0, obs = NULL) ->
+ *   wh_replay_put(stage 1) -> wh_reset(mask = that step's dones, philox draws, variable_n)
+ * followed by wh_observe / wh_observe_x of the final state into obs / xfrag (either or both may be
+ * NULL; xfrag 16-byte aligned; a second launch).  policy = WH_POLICY_EXTERNAL steps with `actions`
+ * (int32 [B,NA]; steps <= 1), WH_POLICY_GREEDY / WH_POLICY_RANDOM with the device policy and
+ * random_action_prob p, whose actions are recorded as wh_policy reports them.  rewards [steps,B,NA]
+ * and dones [steps,B] are optional live copies of what the ring receives; `stats` as in wh_rollout.
+ * WH_EINVAL: ring NULL or capacity < 1, slot outside [0, capacity), steps < 0 or > capacity, policy
+ * not 0 / 1 / 2, policy 0 with steps > 1, p outside [0, 1], bins without episode_return, xfrag
+ * misaligned; for B > 0 and steps > 0 a NULL ring array, or policy 0 without actions.  B = 0 or
+ * steps = 0 launch nothing.  The host engine returns WH_ENOTSUP when xfrag is given. */
+int wh_replay_record(const wh_config* cfg, int64_t B, uint32_t* state, const wh_replay_ring* ring, int64_t slot,
+                     int32_t steps, int32_t policy, float p, const int32_t* actions,
+                     float* rewards, uint8_t* dones, float* obs, void* xfrag,
+                     const wh_episode_stats* stats, int32_t variable_n, uint64_t seed, int64_t env_offset, void* stream);
 
 /* Outputs of wh_replay_gather for M samples; any may be NULL, not all.  obs / next_obs are the rows
  * of wh_observe on side 0 / side 1, xfrag / next_xfrag wh_observe_x's operand for a batch of M envs

@@ -89,6 +89,8 @@ struct StepCall {
   void* xfrag;              // wh_vector_step_x
   uint32_t* state_out;      // wh_sampler_step_to
   const wh_episode_stats* stats;
+  const wh_replay_ring* ring;   // wh_replay_record: every step recorded, step k into slot (slot + k) % capacity
+  int64_t slot;
   int32_t steps, phase, autoreset, variable_n;   // (the two flags as 0 / 1)
   uint64_t seed;
   int64_t env_offset;
@@ -270,6 +272,29 @@ inline int replay_put_call(Shape* g, const wh_config* cfg, int64_t B, const wh_r
   const int rc = check_config(cfg, g);
   if (rc) return rc;
   return ((B > 0 && !state) || B < 0) ? WH_EINVAL : WH_OK;
+}
+
+// wh_replay_record: `steps` recorded steps (external actions: one), then the rows of the final state
+inline int replay_record_call(StepCall* c, const wh_config* cfg, int64_t B, uint32_t* state, const wh_replay_ring* ring,
+                              int64_t slot, int32_t steps, int32_t policy, float p, const int32_t* actions,
+                              float* rewards, uint8_t* dones, float* obs, void* xfrag, const wh_episode_stats* stats,
+                              int32_t variable_n, uint64_t seed, int64_t env_offset) {
+  if (!ring_ok(ring) || slot < 0 || slot >= ring->capacity || steps < 0 || steps > ring->capacity) return WH_EINVAL;
+  if (policy != POLICY_EXTERNAL && !policy_ok(policy)) return WH_EINVAL;
+  if (policy == POLICY_EXTERNAL && steps > 1) return WH_EINVAL;   // one action set, one step
+  if (!p_ok(p) || !stats_ok(stats) || (uintptr_t)xfrag % 16 != 0) return WH_EINVAL;
+  if (B > 0 && steps > 0) {
+    if (!ring->states || !ring->actions || !ring->rewards || !ring->dones) return WH_EINVAL;
+    if (policy == POLICY_EXTERNAL && !actions) return WH_EINVAL;
+  }
+  begin(c, B, state, seed, env_offset);
+  rollout_options(c, steps, policy, p, rewards, dones, stats, 1, variable_n);
+  c->actions = actions;
+  c->obs = obs;
+  c->xfrag = xfrag;
+  c->ring = ring;
+  c->slot = slot;
+  return finish(c, cfg);
 }
 
 inline bool batch_has_frags(const wh_replay_batch* b) { return b->xfrag || b->next_xfrag; }

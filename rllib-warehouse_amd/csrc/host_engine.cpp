@@ -506,7 +506,9 @@ void fold_episode(const wh_episode_stats* st, uint32_t n, uint32_t ret) {
 // One env of a checked step-family call (abi_args.h): c.steps times [policy ->] step -> rewards /
 // dones -> episode-return fold -> auto-reset on an unmasked env, then its rows.  wh_step (phases,
 // injected regeneration draws), wh_rollout (a policy, K steps, returns), wh_vector_step (a mask,
-// rows) and wh_sampler_step (a policy, rows) are this with the options each one sets.
+// rows) and wh_sampler_step (a policy, rows) are this with the options each one sets.  With a ring
+// (wh_replay_record) every step is recorded: the env's record and actions before the step, its
+// record, rewards and done flag after it and before the reset.
 void drive_env(const Geo& g, const wh_abi::StepCall& c, int64_t e) {
   const int64_t B = c.B;
   const uint32_t k0 = wh_abi::lo32(c.seed), k1 = wh_abi::hi32(c.seed), gid = (uint32_t)(c.env_offset + e);
@@ -523,11 +525,30 @@ void drive_env(const Geo& g, const wh_abi::StepCall& c, int64_t e) {
         policy_env(g, s, c.policy, c.p, k0, k1, gid, acts);
         a = acts;
       }
+      // the ring entry of this step, and its side-0 record ((slot * 2 + side) * B + e)
+      const int64_t ent = c.ring ? ((c.slot + k) % c.ring->capacity) * B + e : 0;
+      uint32_t* rec = c.ring ? c.ring->states + (2 * ent - e) * g.words : nullptr;
+      if (c.ring) {
+        // side 0: the words just loaded (step 0), else the state the previous step (and reset) left
+        if (k == 0)
+          for (int w = 0; w < g.words; ++w) rec[w] = c.state[(int64_t)w * B + e];
+        else
+          store(g, rec, 1, 0, s);   // (a record is a one-env word-plane state)
+        for (int i = 0; i < g.NA; ++i) {
+          const uint32_t act = (uint32_t)a[i];
+          c.ring->actions[ent * g.NA + i] = (uint8_t)(act > 8u ? 4u : act);
+        }
+      }
       const StepOut o = step_env(g, s, a, c.order ? c.order + e * c.ol : nullptr, c.ol,
                                  c.regen ? c.regen + e * 2 * g.R : nullptr, k0, k1, gid, c.phase);
       const int64_t row = (int64_t)k * B + e;
       float r = 0.0f;
       for (int i = 0; i < g.NA; ++i) r += o.rew[i];
+      if (c.ring) {   // side 1: the stepped state, before any reset
+        store(g, rec + B * g.words, 1, 0, s);
+        for (int i = 0; i < g.NA; ++i) c.ring->rewards[ent * g.NA + i] = o.rew[i];
+        c.ring->dones[ent] = o.done ? 1 : 0;
+      }
       if (c.phase != WH_PHASE_REGEN) {
         if (c.rewards)
           for (int i = 0; i < g.NA; ++i) c.rewards[row * g.NA + i] = o.rew[i];
@@ -764,6 +785,22 @@ int wh_replay_put(const wh_config* cfg, int64_t B, const wh_replay_ring* ring, i
       ring->dones[slot * B + e] = dones[e];
     }
   }
+  return WH_OK;
+}
+
+// `steps` recorded steps per env (drive_env with a ring), then the rows of the final state
+int wh_replay_record(const wh_config* cfg, int64_t B, uint32_t* state, const wh_replay_ring* ring, int64_t slot,
+                     int32_t steps, int32_t policy, float p, const int32_t* actions, float* rewards, uint8_t* dones,
+                     float* obs, void* xfrag, const wh_episode_stats* stats, int32_t variable_n, uint64_t seed,
+                     int64_t env_offset, void*) {
+  wh_abi::StepCall c;
+  Geo g;
+  int rc = wh_abi::replay_record_call(&c, cfg, B, state, ring, slot, steps, policy, p, actions, rewards, dones, obs,
+                                      xfrag, stats, variable_n, seed, env_offset);
+  if (rc || (rc = make_geo(c.g, &g))) return rc;
+  if (xfrag) return WH_ENOTSUP;   // the fragment operand is a device format
+  if (B == 0 || steps == 0) return WH_OK;
+  run_envs(g, c, 1024);
   return WH_OK;
 }
 

@@ -56,6 +56,7 @@ namespace {
 #include "step_loops.h"     // run_steps, FastRun, run_steps_fast, k_step, k_reset, the WH_TIMING stamps
 #include "observe.h"        // ObsSrc, stream_rows / stream_frags, the image build, k_observe
 #include "replay.h"         // k_replay_put, k_replay_gather
+#include "step_record.h"    // RecordParams, k_step_record: the recorded step (wh_replay_record)
 #include "prio.h"           // k_prio_fill, k_prio_update, k_prio_sample
 #include "sac.h"            // k_sac_td (the row arithmetic: sac_formula.h, shared with the host engine)
 #include "sampler.h"        // FImg, SampLds, write_image, k_sampler
@@ -177,6 +178,7 @@ struct Kernels {
   void (*observe[4])(const uint32_t*, int64_t, int, const uint32_t*, float*, int, uint4*);   // kObsEB[i] envs per WG
   void (*observe_chunk)(const uint32_t*, int64_t, int, const uint32_t*, float*, int, uint4*);   // kObsChunk float4s per WG
   void (*replay_put)(PutParams);
+  void (*step_record[3])(RecordParams);   // [policy]: the recorded step (k_step_record)
   void (*replay_gather[4])(GatherParams);   // kObsEB[i] samples per WG (the instances the gather uses: 0, 2, 3)
   int tblw, nv;
 };
@@ -240,6 +242,9 @@ Kernels make_kernels() {
   k.observe[3] = k_observe<C, kObsEB[3]>;
   k.observe_chunk = kObsChunk > 0 ? k_observe<C, kObsEB[0], kObsChunk> : nullptr;
   k.replay_put = k_replay_put<C>;
+  k.step_record[0] = k_step_record<C, POL_EXTERNAL>;
+  k.step_record[1] = k_step_record<C, POL_GREEDY>;
+  k.step_record[2] = k_step_record<C, POL_RANDOM>;
   k.replay_gather[0] = k_replay_gather<C, kObsEB[0]>;
   k.replay_gather[1] = nullptr;
   k.replay_gather[2] = k_replay_gather<C, kObsEB[2]>;
@@ -867,6 +872,30 @@ int wh_replay_gather(const wh_config* cfg, int64_t B, const wh_replay_ring* ring
   hipLaunchKernelGGL(k->replay_gather[sel], dim3((unsigned)(groups * (next ? 2 : 1))), dim3(BT), 0,
                      (hipStream_t)stream, a);
   return hip_err(hipGetLastError());
+}
+
+// `steps` recorded steps in one launch (csrc/step_record.h), then the rows of the final state through
+// k_observe: the ring bytes, state, rewards, dones, metrics and draws of [wh_policy ->] put(0) ->
+// wh_vector_step(autoreset = 0) -> put(1) -> wh_reset(mask = dones), `steps` times.
+int wh_replay_record(const wh_config* cfg, int64_t B, uint32_t* state, const wh_replay_ring* ring, int64_t slot,
+                     int32_t steps, int32_t policy, float p, const int32_t* actions, float* rewards, uint8_t* dones,
+                     float* obs, void* xfrag, const wh_episode_stats* stats, int32_t variable_n, uint64_t seed,
+                     int64_t env_offset, void* stream) {
+  StepCall c;
+  int rc = wh_abi::replay_record_call(&c, cfg, B, state, ring, slot, steps, policy, p, actions, rewards, dones, obs,
+                                      xfrag, stats, variable_n, seed, env_offset);
+  if (rc) return rc;
+  const Kernels* k;
+  const uint32_t* tab;
+  const bool empty = B == 0 || steps == 0;
+  rc = locate(c.g, empty ? 0 : B, stream, &k, &tab);
+  if (rc || empty) return rc;
+  const RecordParams a{step_params(c, tab), ring->states, ring->actions, ring->rewards, ring->dones, slot,
+                       ring->capacity, c.g.words};
+  hipLaunchKernelGGL(k->step_record[policy], grid_for(B), dim3(BT), 0, (hipStream_t)stream, a);
+  rc = hip_err(hipGetLastError());
+  if (rc || (!obs && !xfrag)) return rc;
+  return observe_launch(c.g, k, tab, B, state, obs, xfrag, stream);
 }
 
 // ---- replay priorities (csrc/prio.h).  abi_args.h has checked the call.

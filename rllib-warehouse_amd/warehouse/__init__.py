@@ -14,12 +14,12 @@ from .batched import BatchedWarehouse, EpisodeStats  # noqa: F401
 from .vector import WarehouseBaseEnv, WarehouseVectorEnv  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401
 from .sac import QNetwork, SACCritic  # noqa: F401
-from .policy import forward_many  # noqa: F401
+from .policy import forward_many, policy_collect  # noqa: F401
 
 __all__ = []
 __all__.extend(core.__all__)
 __all__.extend(variants.__all__)
 __all__ += ["BatchedWarehouse", "EpisodeStats", "WarehouseVectorEnv", "WarehouseBaseEnv", "ReplayBuffer",
-            "SACCritic", "QNetwork", "forward_many"]
+            "SACCritic", "QNetwork", "forward_many", "policy_collect"]
 
 name = "warehouse"

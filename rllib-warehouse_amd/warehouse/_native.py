@@ -33,6 +33,7 @@ WH_PHASE_ALL = 0
 WH_PHASE_PRE_REGEN = 1
 WH_PHASE_REGEN = 2
 
+WH_POLICY_EXTERNAL = 0   # the caller's actions (wh_replay_record)
 WH_POLICY_GREEDY = 1
 WH_POLICY_RANDOM = 2
 
@@ -45,7 +46,7 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_check_read", "wh_rollout_prepare", "wh_launch_run", "wh_launch_run_timed", "wh_launch_free",
            "wh_sampler_step", "wh_sampler_step_to", "wh_sampler_rollout", "wh_vector_step_x",
            "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide",
-           "wh_replay_put", "wh_replay_gather",
+           "wh_replay_put", "wh_replay_gather", "wh_replay_record",
            "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample",
            "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi")
 
@@ -213,6 +214,8 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_replay_put.argtypes = [_CFG, _I64, ctypes.POINTER(WhReplayRing), _I64, _I32, _P, _P, _P, _P, _P]
     S.wh_replay_gather.argtypes = [_CFG, _I64, ctypes.POINTER(WhReplayRing), _I64, _I64, _P, _U64, _U64,
                                    ctypes.POINTER(WhReplayBatch), _P]
+    S.wh_replay_record.argtypes = [_CFG, _I64, _P, ctypes.POINTER(WhReplayRing), _I64, _I32, _I32, _F32, _P, _P, _P,
+                                   _P, _P, _ST, _I32, _U64, _I64, _P]
     _PT = ctypes.POINTER(WhReplayPrio)
     S.wh_replay_prio_query.argtypes = [_I64, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I32)]
     S.wh_replay_prio_fill.argtypes = [_PT, _I64, _I64, _I32, ctypes.c_uint32, _P]

@@ -284,3 +284,24 @@ def policy_rollout(env, net: MLPPolicy, steps: int, *, explore: bool = False, se
         if record is not None:
             record(s, acts, rew, done)
     return obs
+
+
+def policy_collect(buf, net: MLPPolicy, steps: int, *, explore: bool = True, seed: int = 0, first_step: int = 0):
+    """policy_rollout's loop recording into a ReplayBuffer: per step one network forward over all
+    B x NA rows, then buf.step -- the recorded step and the next rows.  A bf16 network reads the
+    fragment operand (`buf.step(acts, operand="fragments")`), an f32 network the float32 rows.  The
+    trajectory, the actions and the ring are those of policy_rollout with a recorder.  Returns the
+    last step's observations (the fragment buffer or the obs tensor)."""
+    env = buf.env
+    B, NA = env.B, env.agent_slots
+    acts = torch.empty((B, NA), dtype=torch.int32, device=env.device)
+    frag = net.precision == "bf16"
+    obs = env.observe_x() if frag else env.observe()
+    for s in range(steps):
+        if frag:
+            net.forward_x(obs, B * NA, explore=explore, seed=seed, step=first_step + s, actions=acts.view(-1))
+            obs, _, _ = buf.step(acts, operand="fragments")
+        else:
+            net(obs.view(B * NA, -1), explore=explore, seed=seed, step=first_step + s, actions=acts.view(-1))
+            obs, _, _ = buf.step(acts)
+    return obs

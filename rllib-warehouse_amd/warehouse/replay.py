@@ -10,6 +10,7 @@ packed states, in one launch.
 
     buf = ReplayBuffer(env, capacity=200)
     obs, rew, done = buf.step(actions)           # a recorded vector_step(autoreset=True)
+    obs, rew, done = buf.collect(100, "greedy", 0.1)   # 100 recorded sampler steps, one launch
     batch = buf.sample(64)                       # obs, next_obs, actions, rewards, dones, n, idx_out
 
 With `prioritized=True` the buffer also keeps a priority tree over its entries (include/
@@ -35,7 +36,14 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .batched import BatchedWarehouse, _check_out, _dev_i32
+from .batched import POLICIES, BatchedWarehouse, _check_out, _dev_i32
+
+# fused=None takes the one record launch (wh_replay_record) on every lane-per-env env: at each measured
+# shape its median is below the five launches' minimum over the rounds (DESIGN.md §5.12,
+# profiles/replay_record_probe.txt; one MI355X, us per recorded step with f32 rows, record launch /
+# five launches): Medium-8 B = 65,536 45.1 / 60.0, B = 4,096 17.6 / 26.9, B = 256 16.0 / 26.0,
+# Large-16 B = 65,536 120.2 / 140.6; with the fragment operand 39.4 / 52.6, 19.7 / 29.3, 18.5 / 26.4,
+# 91.8 / 117.0.  So there is no batch-size threshold to keep.
 
 _SIDES = (("obs", "next_obs"), ("xfrag", "next_xfrag"), ("state", "next_state"))
 
@@ -45,9 +53,14 @@ class ReplayBuffer:
     the env's device with the env's engine (device="cpu": the host engine, no fragments)."""
 
     def __init__(self, env: BatchedWarehouse, capacity: int, prioritized: bool = False, alpha: float = 0.6,
-                 eps: float = 1e-6):
+                 eps: float = 1e-6, fused: Optional[bool] = None):
         """`prioritized`: keep a priority tree (RLlib's `prioritized_replay`), with RLlib's
-        `prioritized_replay_alpha` and `prioritized_replay_eps` as `alpha` and `eps`."""
+        `prioritized_replay_alpha` and `prioritized_replay_eps` as `alpha` and `eps`.
+        `fused`: True records a step() / collect() inside the step launch (wh_replay_record: one
+        launch, plus the rows), False with the five launches put, step, put, reset, observe; None
+        (default) takes the one launch too (it measured faster at every shape).  An env with
+        lanes_per_env=16 always takes the five launches.  Both routes write the same bytes;
+        `last_fused` says which one the last step() or collect() took."""
         capacity = int(capacity)
         if capacity < 1:
             raise ValueError(f"capacity: at least 1 slot, got {capacity}")
@@ -64,6 +77,8 @@ class ReplayBuffer:
         self._filled = 0
         self._draw = 0
         self._out: Dict[tuple, torch.Tensor] = {}
+        self.fused = None if fused is None else bool(fused)
+        self.last_fused: Optional[bool] = None
         self.prioritized = bool(prioritized)
         if self.prioritized:
             self._init_tree(float(alpha), float(eps))
@@ -133,18 +148,102 @@ class ReplayBuffer:
         self._cursor = (self._cursor + 1) % self.capacity
         self._filled = min(self._filled + 1, self.capacity)
 
-    def step(self, actions, observe: bool = True):
-        """env.vector_step(actions, autoreset=True), recorded: the same trajectory (philox draws,
-        Train-variant n redraws, episode stats) and the same return value."""
+    def _record_route(self) -> bool:
+        """Does the next recorded step take the one record launch (wh_replay_record)?  The wide
+        (16 lanes per env) form has no record kernel; `fused=None` takes it wherever there is one."""
+        return self.env.lanes_per_env == 1 and self.fused is not False
+
+    def _rows(self, observe: bool, frag: bool):
+        """The output of the step's rows: (obs tensor or None, fragment buffer or None)."""
         e = self.env
-        a = _dev_i32(actions, e.device, (e.B, e.agent_slots))
+        if not observe:
+            return None, None
+        if frag:
+            return None, e._xfrag_buffer()
+        if e._obs is None:
+            e._obs = torch.empty((e.B, e.agent_slots, e.obs_len), dtype=torch.float32, device=e.device)
+        return e._obs, None
+
+    def _record(self, steps: int, policy: int, p: float, actions, rewards, dones, obs, xf) -> None:
+        e = self.env
+        e._call("wh_replay_record", e.state.data_ptr(), ctypes.byref(self._ring), self._cursor, steps, policy, p,
+                None if actions is None else actions.data_ptr(), rewards.data_ptr(), dones.data_ptr(),
+                None if obs is None else obs.data_ptr(), None if xf is None else xf.data_ptr(),
+                None if e.stats is None else e.stats.ref, int(e.train), e.seed, e.env_offset, e.stream)
+
+    def _unfused_step(self, a) -> None:
+        """One recorded step as five launches: put, step without auto-reset, put, reset of the done envs."""
+        e = self.env
         self._put(self._cursor, 0, a)
         e.vector_step(a, autoreset=False, observe=False)
         self._put(self._cursor, 1)
         e.reset(mask=e.dones)
-        obs = e.observe() if observe else None
+
+    @staticmethod
+    def _operand(operand: str, host: bool) -> bool:
+        if operand not in ("rows", "fragments"):
+            raise ValueError("operand must be 'rows' or 'fragments'")
+        if operand == "fragments" and host:
+            raise nat.WarehouseNativeError("the fragment operand is a device format (the host engine has none)")
+        return operand == "fragments"
+
+    def step(self, actions, observe: bool = True, operand: str = "rows"):
+        """env.vector_step(actions, autoreset=True), recorded: the same trajectory (philox draws,
+        Train-variant n redraws, episode stats) and the same return value.  operand="fragments"
+        (device only) returns the env's observe_x() buffer -- the policy network's layer-0 operand,
+        what vector_step_x returns -- instead of the f32 rows.  On a lane-per-env env the step is
+        one record launch (wh_replay_record) plus the rows (see `fused`); `last_fused` says which
+        route ran."""
+        e = self.env
+        frag = self._operand(operand, e.host)
+        a = _dev_i32(actions, e.device, (e.B, e.agent_slots))
+        self.last_fused = self._record_route()
+        if self.last_fused:
+            obs, xf = self._rows(observe, frag)
+            self._record(1, nat.WH_POLICY_EXTERNAL, 0.0, a, e.rewards, e.dones, obs, xf)
+        else:
+            self._unfused_step(a)
+            obs, xf = None, None
+            if observe:
+                obs, xf = (None, e.observe_x()) if frag else (e.observe(), None)
         self.advance()
-        return obs, e.rewards, e.dones
+        return (xf if frag else obs), e.rewards, e.dones
+
+    def collect(self, steps: int, policy: str = "greedy", p: float = 0.0, observe: bool = True,
+                operand: str = "rows"):
+        """`steps` (<= capacity) recorded sampler steps with the device policy -- env.policy(policy, p)
+        then step(), `steps` times -- in one launch on a lane-per-env env, so a buffer fills without
+        a Python loop.  Returns (the final state's obs or fragment buffer, or None; rewards
+        [steps,B,NA]; dones [steps,B]), the two outputs fresh tensors."""
+        e = self.env
+        steps = int(steps)
+        if not 0 <= steps <= self.capacity:
+            raise ValueError(f"steps: 0 .. capacity ({self.capacity}), got {steps}")
+        frag = self._operand(operand, e.host)
+        pol = POLICIES[policy]
+        rew = torch.empty((steps, e.B, e.agent_slots), dtype=torch.float32, device=e.device)
+        done = torch.empty((steps, e.B), dtype=torch.uint8, device=e.device)
+        self.last_fused = self._record_route() and steps > 0
+        if self.last_fused:
+            obs, xf = self._rows(observe, frag)
+            self._record(steps, pol, float(p), None, rew, done, obs, xf)
+            if self.prioritized:   # the new slots enter at the largest priority: the range, or its two parts
+                first = min(steps, self.capacity - self._cursor)
+                for slot, count in ((self._cursor, first), (0, steps - first)):
+                    if count:
+                        self._prio_call("wh_replay_prio_fill", slot * e.B, count * e.B, 1, 0, e.stream)
+            self._cursor = (self._cursor + steps) % self.capacity
+            self._filled = min(self._filled + steps, self.capacity)
+        else:
+            for k in range(steps):
+                self._unfused_step(e.policy(policy, p))
+                rew[k].copy_(e.rewards)
+                done[k].copy_(e.dones)
+                self.advance()
+            obs, xf = None, None
+            if observe:
+                obs, xf = (None, e.observe_x()) if frag else (e.observe(), None)
+        return (xf if frag else obs), rew, done
 
     def update_priorities(self, idx, priorities) -> None:
         """Entry idx[m] (slot * B + env, what sample() returned as idx_out) gets the priority

@@ -16,6 +16,11 @@ then ReplayBuffer.step against vector_step(autoreset=True) per step, and one Lar
 against (c).  --gather-only launches (a) rows alone, for a counter pass of its own:
     rocprofv3 --pmc FETCH_SIZE -T --output-format csv -d DIR -o run -- python3 tools/replay_probe.py --gather-only
 Algorithmic bytes of a gather: the rows (or fragments) written plus 2 M records read.
+
+--only record times the recorded step alone: ReplayBuffer.step with fused=False (put,
+step, put, reset, observe), with fused=True (wh_replay_record + observe) and vector_step(autoreset=True),
+then collect(5) against 5 x step, each with f32 rows and with the fragment operand, at Medium-8
+B = 65,536 / 4,096 / 256 and Large-16 B = 65,536.
 """
 import argparse
 import os
@@ -144,12 +149,51 @@ def probe(variant, na, B, cap, M, rounds, reps, baseline=True, NBUF=3, gather_on
             f"{med['ReplayBuffer.step (put, step, put, reset, observe)'] / med['vector_step(autoreset=True)']:.3f}")
 
 
+def probe_record(variant, na, B, rounds, reps, cap=8):
+    """The recorded step's routes at one shape: three envs in one state, one buffer per route."""
+    dev = torch.device("cuda", 0)
+    envs = [warehouse.BatchedWarehouse(variant, B, na, seed=3, device=dev) for _ in range(3)]
+    for e in envs:
+        e.reset()
+        e.stagger(torch.arange(B, device=dev) % 7)
+    unfused = warehouse.ReplayBuffer(envs[0], cap, fused=False)
+    fused = warehouse.ReplayBuffer(envs[1], cap, fused=True)
+    plain = envs[2]
+    acts = plain.policy("greedy", 0.1).clone()
+    ring_mb = sum(t.numel() * t.element_size() for t in (fused.states, fused.actions, fused.rewards, fused.dones)) / 1e6
+    say(f"# record: {variant}-{na}  B = {B}  capacity = {cap} (ring {ring_mb:.1f} MB)  "
+        f"record writes of a step {2 * B * envs[0].layout.words_per_env * 4 / 1e6:.2f} MB")
+    for operand in ("rows", "fragments"):
+        step_x = plain.vector_step_x if operand == "fragments" else plain.vector_step
+        variants = [(f"step fused=False, {operand}", lambda r: unfused.step(acts, operand=operand)),
+                    (f"step fused=True, {operand}", lambda r: fused.step(acts, operand=operand)),
+                    (f"vector_step(autoreset=True), {operand}", lambda r: step_x(acts, autoreset=True)),
+                    (f"5 x step fused=False + policy, {operand}",
+                     lambda r: [unfused.step(envs[0].policy("greedy", 0.1), operand=operand) for _ in range(5)]),
+                    (f"collect(5) fused=True, {operand}", lambda r: fused.collect(5, "greedy", 0.1, operand=operand))]
+        for _, fn in variants:
+            for r in range(4):
+                fn(r)
+        torch.cuda.synchronize()
+        times = {name: [] for name, _ in variants}
+        for _ in range(rounds):                             # interleaved
+            for name, fn in variants:
+                times[name].append(time_us(fn, reps if "5" not in name.split(",")[0] else max(reps // 5, 4)))
+        med = {name: report(name, times[name]) for name, _ in variants}
+        names = [n for n, _ in variants]
+        bar = min(times[names[0]])
+        say(f"fused / unfused = {med[names[1]] / med[names[0]]:.3f}   fused / vector_step = {med[names[1]] / med[names[2]]:.3f}   "
+            f"fused median {'below' if med[names[1]] < bar else 'NOT below'} the unfused minimum {bar:.2f}")
+        say(f"collect(5) / 5 x step = {med[names[4]] / med[names[3]]:.3f}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--reps", type=int, default=40)
     ap.add_argument("--small", action="store_true", help="a rehearsal at toy sizes")
+    ap.add_argument("--only", choices=["record"], default=None, help="record: the recorded step's routes alone")
     ap.add_argument("--gather-only", action="store_true",
                     help="12 launches of (a) rows at the Medium-8 shape and nothing else: the run a counter pass wraps")
     a = ap.parse_args()
@@ -157,7 +201,15 @@ def main():
     from warehouse import _native
 
     say(f"# {_native.lib().wh_version().decode()}  {torch.cuda.get_device_name(0)}")
-    if a.gather_only:
+    if a.only == "record":
+        if a.small:
+            probe_record("medium", 8, 300, 2, 5)
+            probe_record("large", 16, 100, 2, 5)
+        else:
+            for B in (65536, 4096, 256):
+                probe_record("medium", 8, B, a.rounds, a.reps)
+            probe_record("large", 16, 65536, a.rounds, a.reps)
+    elif a.gather_only:
         probe("medium", 8, 65536, 16, 32768, 0, 0, gather_only=True)
     elif a.small:
         probe("medium", 8, 1024, 4, 512, 2, 3)
