@@ -54,28 +54,15 @@ constexpr bool rows_nt() {
   return C::NAM * C::L * 4 <= 1024 || C::NAM * C::L * 4 > 4096;
 }
 
-#ifndef WH_REV_SPLIT_MAX_NAM   // agent counts up to which the move loop has the no-reverse-key variant
-#define WH_REV_SPLIT_MAX_NAM 9
-#endif
-constexpr int kRevSplitMaxNam = WH_REV_SPLIT_MAX_NAM;
+// Agent counts up to which the move loop has the no-reverse-key variant (Large-16, whose step loop
+// spills, measured 1 % slower with it).
+constexpr int kRevSplitMaxNam = 9;
 // Turns between the move loop's dependent pickup lookups (cell -> point row, point -> target byte,
 // target -> delivery cell, then the decision): each lookup is issued kPickDist turns after the one
 // it depends on, so its LDS latency is covered by that many turns of the serial chain.  Two turns:
 // Medium-8 -1.0 %, Large-16 -1.0 % per 200-step launch against one (profiles/r05_pick_ab.txt); three
-// turns +1.3 % / +0.9 % against two (profiles/r05_tune_ab.txt).  -DWH_PICK_DIST=1 / 3 (A/B).
-#ifndef WH_PICK_DIST
-#define WH_PICK_DIST 2
-#endif
-constexpr int kPickDist = WH_PICK_DIST;
-// k_step's fused greedy loop is rotated: the request walk of step t + 1 (policy_walk: nine dependent
-// LDS lookups) is issued right after step t's regeneration, and its results cross the back-edge in
-// registers, so their latency is behind the loop branch instead of in front of the policy's distance
-// tests; a reset redoes the walk.  -DWH_NO_WALK_ROTATE: the walk at the head of its own step (A/B).
-#ifndef WH_NO_WALK_ROTATE
-constexpr bool kWalkRotate = true;
-#else
-constexpr bool kWalkRotate = false;
-#endif
+// turns +1.3 % / +0.9 % against two (profiles/r05_tune_ab.txt).
+constexpr int kPickDist = 2;
 
 constexpr uint32_t IDLE = 0xFF00FF00u;    // delivery-target bytes of an idle agent
 constexpr uint32_t XY16 = 0x00FF00FFu;    // position bytes of an agent word
@@ -242,6 +229,8 @@ __device__ __forceinline__ uint32_t action_of(uint32_t d) {
   const short2v v = as_s2(d);
   return (uint32_t)(3 * ((int)v.x + 1) + ((int)v.y + 1));
 }
+// an action outside 0 .. 8 is "stay"
+__device__ __forceinline__ uint32_t valid_action(uint32_t action) { return action > 8u ? 4u : action; }
 
 // Rare wave-uniform branches of the step loop (expiry pass, grid rebuild, resets, random moves): marked
 // cold so that block placement keeps their code out of the hot path's instruction stream.
@@ -262,9 +251,7 @@ __device__ __forceinline__ uint32_t action_of(uint32_t d) {
 // that consume it to 8 / 16 bits and widens the results again, a v_and per lookup in the step loop.
 __device__ __forceinline__ uint32_t lds_byte(const uint8_t* p) {
   uint32_t v = *p;
-#ifndef WH_NO_BYTE_OPAQUE   // (A/B: the byte as LLVM types it)
   asm("" : "+v"(v));
-#endif
   return v;
 }
 
@@ -461,14 +448,10 @@ __device__ __forceinline__ void load_env_finish(Regs<C>& s, Lds<C>& L, const Raw
   for (int w = 0; w < C::PW; ++w)
     early |= nz_hi(r.pt[w]) & swar_lt(swar_sub(r.pm[w], (t0 & 0xFFu) * 0x01010101u), thr * 0x01010101u);
   // (LLVM folds this select of two uniform values into every step's expiry test, `any early || t >= W`,
-  // five instructions there.  -DWH_WSKIP_SCALAR pins it in a scalar register through v_readfirstlane,
-  // which leaves one compare in the step -- and measured slower: Medium-8 +0.8 %, Large-16 +5 % per
-  // 200-step launch, profiles/fused_constants_ab.txt)
-#ifdef WH_WSKIP_SCALAR
-  s.wskip = (uint32_t)__builtin_amdgcn_readfirstlane((int)(__any(early != 0u) ? 0u : W));
-#else
+  // five instructions there.  Pinned in a scalar register through v_readfirstlane it left one compare
+  // in the step and measured slower -- Medium-8 +0.8 %, Large-16 +5 % per 200-step launch,
+  // profiles/fused_constants_ab.txt -- so it is not.)
   s.wskip = __any(early != 0u) ? 0u : W;
-#endif
 }
 
 template <class C>

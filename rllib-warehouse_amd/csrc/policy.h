@@ -8,7 +8,7 @@
 // the sentinel, so every agent's "nearest request" is the null cell, which is where the
 // reference's reset observation sends the greedy solver (availability 0, core.py:233-236).
 // Reads only the request mask and the fresh bit, so the fused step loop can run it for step t + 1
-// as soon as step t's regeneration is done (run_steps_fast, kWalkRotate).
+// as soon as step t's regeneration is done (run_steps_fast's ROT).
 // STEPPED: the state comes straight out of a step, which clears the fresh bit, so the mask is used as
 // it is (the bitop3 selects are opaque to LLVM: it cannot fold them on the constant).
 template <class C, bool STEPPED = false>

@@ -1,5 +1,5 @@
 // step_env.h -- one step of one env held in registers (device code; included by warehouse_amd.hip after
-// device_vocab.h): step_env, the image offsets of the observation values (obs_src), the reward-row
+// device_vocab.h): step_env and its expiry and delivery phases, the image offsets of the observation values (obs_src), the reward-row
 // writer (store_rewards) and assert mode's check_env.
 // ----------------------------------------------------------------------------- step
 // core.py:267-368 on one env held in registers.  Returns done.  No data-dependent branches:
@@ -49,6 +49,89 @@ struct OKeys {
   uint16_t k[4 * C::NAM][BT];
 };
 
+// Request expiry (core.py:303-306), 4 pickup points per op.  Timer bytes hold the low 8 bits of the
+// step at which the request expires (opened at t0 with wait W: t0 + W, the step whose decrement would
+// reach 0), so nothing is decremented.  A request opened at t0 >= 0 cannot expire before step W, so
+// waves with every t < W skip the phase (with T = W, 199 of 200 steps) unless they were loaded from a
+// state outside that invariant (s.wskip).  Run before the move: expiry reads no positions and the
+// move reads no requests, so the two commute, and the pickup table is final before the move loop --
+// which lets its lookups be issued inside it.
+template <class C>
+__device__ __forceinline__ void expire_requests(Regs<C>& s, Lds<C>& L, uint32_t t, int tid, int ablate) {
+  const uint64_t em = (ablate & 4) ? 0ull : __ballot(t >= s.wskip);
+  if (WH_RARE(em != 0) && __popcll(em) == 1 && __ballot(true) == ~0ull) {
+    // one lane of a full wave due (desynchronised episodes): its P pickup cells checked one per
+    // lane of the wave, instead of the whole wave walking every lane's requests
+    const int l = __builtin_ctzll(em), lane = tid & 63, col = (tid & ~63) + l;
+    const uint32_t t8 = (uint32_t)__builtin_amdgcn_readlane(t, l) & 0xFFu;
+    const uint32_t v = lane < C::P ? (uint32_t)L.pkp[lane][col] : 0u;
+    const bool ex = (v & 0xFFu) != 0u && (v >> 8) == t8;
+    if (ex) L.clear_target(lane, col);
+    const uint64_t exm = __ballot(ex);
+    s.am = lane == l ? (s.am & ~exm) : s.am;
+  } else if (WH_RARE(em != 0)) {
+    if (__any(__popcll(s.am) > C::R)) {   // a hand-built state with more than R requests: scan all
+      uint64_t expired = 0;
+#pragma unroll
+      for (int j = 0; j < C::P; ++j) {
+        const uint32_t v = L.pkp[j][tid];
+        const bool ex = (v & 0xFFu) != 0u && (v >> 8) == (t & 0xFFu);
+        if (ex) L.clear_target(j, tid);
+        expired |= (uint64_t)ex << j;
+      }
+      s.am &= ~expired;
+    } else {
+      // walk the (at most R) open requests in the mask, as the policy does; index P (missing
+      // slots) is the scratch row, and its "expiry" is discarded by the j < P test
+      uint32_t mlo = (uint32_t)s.am, mhi = (uint32_t)(s.am >> 32), elo = 0, ehi = 0;
+      const uint32_t t8 = t & 0xFFu;
+#pragma unroll
+      for (int r = 0; r < C::R; ++r) {
+        uint32_t flo, fhi;
+        asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(mlo));   // 0xFFFFFFFF when empty
+        asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(mhi));
+        const uint32_t j = __builtin_elementwise_min(
+            __builtin_elementwise_min(flo, __builtin_elementwise_add_sat(fhi, 32u)), (uint32_t)C::P);
+        const uint32_t v = L.pkp[j][tid];
+        const uint32_t ex = bop3<TA & TB>(mask_z((v >> 8) ^ t8), sgn(j - (uint32_t)C::P), 0xFFFFFFFFu);
+        *reinterpret_cast<uint8_t*>(&L.pkp[msel(ex, j, (uint32_t)C::P)][tid]) = 0;
+        const uint64_t b = 1ull << (j & 63u);
+        elo |= bop3<TA & TB>(ex, (uint32_t)b, 0u);
+        ehi |= bop3<TA & TB>(ex, (uint32_t)(b >> 32), 0u);
+        uint64_t m = ((uint64_t)mhi << 32) | mlo;
+        m &= m - 1ull;
+        mlo = (uint32_t)m;
+        mhi = (uint32_t)(m >> 32);
+      }
+      s.am &= ~(((uint64_t)ehi << 32) | elo);
+    }
+  }
+}
+
+// Deliveries (core.py:354-368): target cell == position (idle agents never match), and the step's
+// rewards from the pickup masks (rewm) and the deliveries.
+// Manhattan distance position -> target cell minus 1 is ONE v_sad_u8 of the agent word against its
+// target bytes doubled ([x, dx, y, dy] vs [dx, dx, dy, dy], accumulator -1): negative exactly when the
+// agent stands on its target (an idle agent's 0xFF bytes never match).  The reward of the pickup or
+// the delivery is folded into the same bitop3 that makes the 1.0f.
+template <class C>
+__device__ __forceinline__ void deliver(Regs<C>& s, const uint32_t (&rewm)[C::NAM], float (&rew)[C::NAM], int ablate) {
+  uint32_t delm[C::NAM];
+#pragma unroll
+  for (int i = 0; i < C::NAM; ++i) delm[i] = 0u;
+  if (!(ablate & 32)) {
+#pragma unroll
+    for (int i = 0; i < C::NAM; ++i) {
+      const uint32_t a = s.ag[i];
+      const uint32_t m = sgn(__builtin_amdgcn_sad_u8(a, __builtin_amdgcn_perm(a, a, 0x03030101u), 0xFFFFFFFFu));
+      s.ag[i] = bop3<(TA & TB) | TC>(m, IDLE, a);
+      delm[i] = m;   // a pickup (interior cell) and a delivery (border cell) never share a step
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < C::NAM; ++i) rew[i] = __uint_as_float(bop3<(TA | TB) & TC>(rewm[i], delm[i], 0x3F800000u));
+}
+
 template <class C, bool ORDERED, bool INJ = true, bool CLAMP = true, bool LAZY = false>
 __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (&dstep)[C::NAM],
                                          const OrderIn& oi,
@@ -70,65 +153,15 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 #pragma unroll
     for (int i = 0; i < C::NAM; ++i) rewm[i] = 0u;
 
-    // ---- request expiry (core.py:303-306), 4 pickup points per op.  Timer bytes hold the low 8
-    //      bits of the step at which the request expires (opened at t0 with wait W: t0 + W, the
-    //      step whose decrement would reach 0), so nothing is decremented.  A request opened at
-    //      t0 >= 0 cannot expire before step W, so waves with every t < W skip the phase (with
-    //      T = W, 199 of 200 steps) unless they were loaded from a state outside that invariant
-    //      (s.wskip).  Run before the move: expiry reads no positions and the move reads no
-    //      requests, so the two commute, and the pickup table is final before the move loop --
-    //      which lets its lookups be issued inside it.
     WH_PHASE_MARK(expire);
-    const uint64_t em = (ablate & 4) ? 0ull : __ballot(t >= s.wskip);
-    if (WH_RARE(em != 0) && __popcll(em) == 1 && __ballot(true) == ~0ull) {
-      // one lane of a full wave due (desynchronised episodes): its P pickup cells checked one per
-      // lane of the wave, instead of the whole wave walking every lane's requests
-      const int l = __builtin_ctzll(em), lane = tid & 63, col = (tid & ~63) + l;
-      const uint32_t t8 = (uint32_t)__builtin_amdgcn_readlane(t, l) & 0xFFu;
-      const uint32_t v = lane < C::P ? (uint32_t)L.pkp[lane][col] : 0u;
-      const bool ex = (v & 0xFFu) != 0u && (v >> 8) == t8;
-      if (ex) L.clear_target(lane, col);
-      const uint64_t exm = __ballot(ex);
-      s.am = lane == l ? (s.am & ~exm) : s.am;
-    } else if (WH_RARE(em != 0)) {
-      if (__any(__popcll(s.am) > C::R)) {   // a hand-built state with more than R requests: scan all
-        uint64_t expired = 0;
-#pragma unroll
-        for (int j = 0; j < C::P; ++j) {
-          const uint32_t v = L.pkp[j][tid];
-          const bool ex = (v & 0xFFu) != 0u && (v >> 8) == (t & 0xFFu);
-          if (ex) L.clear_target(j, tid);
-          expired |= (uint64_t)ex << j;
-        }
-        s.am &= ~expired;
-      } else {
-        // walk the (at most R) open requests in the mask, as the policy does; index P (missing
-        // slots) is the scratch row, and its "expiry" is discarded by the j < P test
-        uint32_t mlo = (uint32_t)s.am, mhi = (uint32_t)(s.am >> 32), elo = 0, ehi = 0;
-        const uint32_t t8 = t & 0xFFu;
-#pragma unroll
-        for (int r = 0; r < C::R; ++r) {
-          uint32_t flo, fhi;
-          asm("v_ffbl_b32 %0, %1" : "=v"(flo) : "v"(mlo));   // 0xFFFFFFFF when empty
-          asm("v_ffbl_b32 %0, %1" : "=v"(fhi) : "v"(mhi));
-          const uint32_t j = __builtin_elementwise_min(
-              __builtin_elementwise_min(flo, __builtin_elementwise_add_sat(fhi, 32u)), (uint32_t)C::P);
-          const uint32_t v = L.pkp[j][tid];
-          const uint32_t ex = bop3<TA & TB>(mask_z((v >> 8) ^ t8), sgn(j - (uint32_t)C::P), 0xFFFFFFFFu);
-          *reinterpret_cast<uint8_t*>(&L.pkp[msel(ex, j, (uint32_t)C::P)][tid]) = 0;
-          const uint64_t b = 1ull << (j & 63u);
-          elo |= bop3<TA & TB>(ex, (uint32_t)b, 0u);
-          ehi |= bop3<TA & TB>(ex, (uint32_t)(b >> 32), 0u);
-          uint64_t m = ((uint64_t)mhi << 32) | mlo;
-          m &= m - 1ull;
-          mlo = (uint32_t)m;
-          mhi = (uint32_t)(m >> 32);
-        }
-        s.am &= ~(((uint64_t)ehi << 32) | elo);
-      }
-    }
+    expire_requests<C>(s, L, t, tid, ablate);
 
     // ---- move + collision, sequential in action-dict order (core.py:275-300)
+    // (This block and the regeneration stay in this body, unlike expiry and delivery.  Either one as a
+    // __forceinline__ function of its own gave every k_step, k_sampler and k_step_record instance
+    // another register allocation -- 18 of Medium-8's 39 kernels; the move block also +8/+9 v_mov_b32
+    // and 74 more lines in the generic greedy k_step -- and nobody has timed those:
+    // profiles/step_env_split_isa.txt.)
     WH_PHASE_MARK(move);
     uint32_t cp[C::NAM], tb[C::NAM], dst[C::NAM];   // pickup lookups (core.py:309-329): cell_row,
                                                     // target byte, delivery cell
@@ -233,7 +266,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
           const uint32_t a = L.agl[who][tid];
           const uint32_t mv = live ? (sact ? sact - 1u : (uint32_t)actions_g[e * na + who]) : 4u;
           const uint32_t p = a & XY16;
-          const uint32_t c = step16<C::D>(p, L.mv(mv > 8u ? 4u : mv));
+          const uint32_t c = step16<C::D>(p, L.mv(valid_action(mv)));
           const bool occupied = (L.occ[c >> 16][tid] >> (c & 31u)) & 1u;
           const uint32_t sum = as_u(as_s2(p) + as_s2(c)), dd = pk_sub_i16(c, p);
           const uint32_t key = (((dd + 1u) & 3u) | ((((dd >> 16) + 1u) & 3u) << 2) | ((sum & 63u) << 4) |
@@ -376,11 +409,7 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
         // Where the reverse-key loop runs exactly for the waves with shared cells, that test is made
         // on its (rare) side of the branch, so the common path has no branch between the pickup
         // tail and regeneration item 0 and the two are scheduled as one block.
-#ifdef WH_NO_PICK_MERGE   // (A/B: the test after the pickup tail)
-        constexpr bool CM_IN_REV = false;
-#else
         constexpr bool CM_IN_REV = LAZY && C::NAM <= kRevSplitMaxNam;
-#endif
         // REV: the exact loop for waves with co-located agents (only a stay's key flipped), else the
         // loop for waves without any (every key flipped).  The lazy grid knows the lanes with shared
         // cells (lg->cm, from the last rebuild; new sharing needs an existing one).  From
@@ -520,31 +549,24 @@ __device__ __forceinline__ bool step_env(Regs<C>& s, Lds<C>& L, const uint32_t (
 
   bool done = false;
   if (phase != PH_REGEN) {
-    // ---- deliveries (core.py:354-368): target cell == position (idle agents never match)
     WH_PHASE_MARK(deliver);
-    // Manhattan distance position -> target cell minus 1 is ONE v_sad_u8 of the agent word against
-    // its target bytes doubled ([x, dx, y, dy] vs [dx, dx, dy, dy], accumulator -1): negative exactly
-    // when the agent stands on its target (an idle agent's 0xFF bytes never match).  The reward of
-    // the pickup or the delivery is folded into the same bitop3 that makes the 1.0f.
-    uint32_t delm[C::NAM];
-#pragma unroll
-    for (int i = 0; i < C::NAM; ++i) delm[i] = 0u;
-    if (!(ablate & 32)) {
-#pragma unroll
-      for (int i = 0; i < C::NAM; ++i) {
-        const uint32_t a = s.ag[i];
-        const uint32_t m = sgn(__builtin_amdgcn_sad_u8(a, __builtin_amdgcn_perm(a, a, 0x03030101u), 0xFFFFFFFFu));
-        s.ag[i] = bop3<(TA & TB) | TC>(m, IDLE, a);
-        delm[i] = m;   // a pickup (interior cell) and a delivery (border cell) never share a step
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < C::NAM; ++i) rew[i] = __uint_as_float(bop3<(TA | TB) & TC>(rewm[i], delm[i], 0x3F800000u));
+    deliver<C>(s, rewm, rew, ablate);
     WH_PHASE_MARK(tail);
     done = t >= T;                                            // core.py:438
     s.hdr = t | (ec ? ec->n16 : n << 16);                     // clears `fresh`
   }
   return done;
+}
+
+// The fused rollout's step (FastRun::step, run_steps_fast): every agent slot in ascending order, all
+// phases, Philox regeneration, the lazy grid; rb and ec may be null (step_env).
+template <class C, bool CLAMP>
+__device__ __forceinline__ bool step_env_fused(Regs<C>& s, Lds<C>& L, const uint32_t (&dstep)[C::NAM], const Keys& k,
+                                               uint32_t gid, int64_t e, uint32_t T, uint32_t W, float (&rew)[C::NAM],
+                                               int tid, int ablate, LazyGrid* lg, const uint4* rb,
+                                               const EnvConst<C>* ec) {
+  return step_env<C, false, false, CLAMP, true>(s, L, dstep, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e,
+                                                C::NAM, PH_ALL, T, W, rew, nullptr, tid, ablate, lg, rb, ec);
 }
 
 // Image offset of output value f of agent row i (sorted-key order, see wh_observe).
@@ -577,6 +599,19 @@ __host__ __device__ constexpr uint32_t obs_src(int i, int f, bool fresh) {
 // store each lane's row with 16/8-byte stores; otherwise lanes write their rows into LDS (the agl
 // scratch, free after the move phase) and read the block back so every global store instruction
 // writes contiguous 16-byte lanes instead of one strided row per lane.
+// One env's row of an even agent count (16- or 8-byte aligned) as 16-byte (8-byte) stores.
+template <class C>
+__device__ __forceinline__ void store_row(float* row, const float (&rew)[C::NAM]) {
+  if constexpr ((C::NAM & 3) == 0) {
+#pragma unroll
+    for (int q = 0; q < C::NAM / 4; ++q)
+      reinterpret_cast<float4*>(row)[q] = make_float4(rew[4 * q], rew[4 * q + 1], rew[4 * q + 2], rew[4 * q + 3]);
+  } else {
+#pragma unroll
+    for (int q = 0; q < C::NAM / 2; ++q) reinterpret_cast<float2*>(row)[q] = make_float2(rew[2 * q], rew[2 * q + 1]);
+  }
+}
+
 template <class C>
 __device__ __forceinline__ void store_rewards(Lds<C>& L, const float (&rew)[C::NAM], float* out,
                                               int64_t B, int64_t e, int na, int tid, bool direct) {
@@ -584,16 +619,7 @@ __device__ __forceinline__ void store_rewards(Lds<C>& L, const float (&rew)[C::N
     // One row of 16-byte (8-byte) stores per lane: the two wave-instructions of a Medium-8 step
     // cover the wave's contiguous 2 KiB block between them (A/B: 5 % faster than the LDS transpose
     // below, whose row writes are 8-way bank conflicts).
-    if ((C::NAM & 3) == 0) {
-      float4* row = reinterpret_cast<float4*>(out + e * na);
-#pragma unroll
-      for (int q = 0; q < C::NAM / 4; ++q)
-        row[q] = make_float4(rew[4 * q], rew[4 * q + 1], rew[4 * q + 2], rew[4 * q + 3]);
-    } else {
-      float2* row = reinterpret_cast<float2*>(out + e * na);
-#pragma unroll
-      for (int q = 0; q < C::NAM / 2; ++q) row[q] = make_float2(rew[2 * q], rew[2 * q + 1]);
-    }
+    store_row<C>(out + e * na, rew);
     return;
   }
   const int lane = tid & 63;

@@ -11,10 +11,10 @@
 #define WH_ABLATE_WORD(a) 0
 #endif
 
-// MOVES[action] as the packed step (core.py:38); an action outside 0 .. 8 is "stay"
+// MOVES[action] as the packed step (core.py:38)
 template <class C>
 __device__ __forceinline__ uint32_t move_of(const Lds<C>& L, uint32_t action) {
-  return L.mv(action > 8u ? 4u : action);
+  return L.mv(valid_action(action));
 }
 
 // the ablation's stand-in for a policy (ablate & 1): moves that cost nothing to compute
@@ -95,18 +95,6 @@ constexpr int kSlotResetMax = 8;
 // per wave (Medium-8), so launches shorter than this reset single lanes from scratch (reset_lane).
 constexpr int kSlotMinSteps = 8;
 
-template <class C>
-__device__ __forceinline__ void store_row(float* row, const float (&rew)[C::NAM]) {
-  if constexpr ((C::NAM & 3) == 0) {
-#pragma unroll
-    for (int q = 0; q < C::NAM / 4; ++q)
-      reinterpret_cast<float4*>(row)[q] = make_float4(rew[4 * q], rew[4 * q + 1], rew[4 * q + 2], rew[4 * q + 3]);
-  } else {
-#pragma unroll
-    for (int q = 0; q < C::NAM / 2; ++q) reinterpret_cast<float2*>(row)[q] = make_float2(rew[2 * q], rew[2 * q + 1]);
-  }
-}
-
 // The ended-episode reset dispatch ("which reset form does this wave take") is written out twice, in
 // FastRun::step and in run_steps_fast: a change to one belongs in the other.  As one __forceinline__
 // helper called from both, every fast k_step instance compiled to another register allocation (SGPR
@@ -160,8 +148,8 @@ struct FastRun {
       policy_steps<C, POLICY, POLICY == POL_GREEDY && !kAblationBuild>(s, L, k, gid, a.p, d);
     }
     float rew[C::NAM];
-    const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, true>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
-                                                (uint32_t)a.T, (uint32_t)a.W, rew, nullptr, tid, ablate, &lg);
+    const bool done = step_env_fused<C, POLICY != POL_GREEDY || kAblationBuild>(s, L, d, k, gid, e, (uint32_t)a.T, (uint32_t)a.W, rew, tid,
+                                                                                 ablate, &lg, nullptr, nullptr);
     if (!(ablate & 64)) {
       store_row<C>(rrow, rew);
       *drow = done ? 1 : 0;
@@ -216,9 +204,12 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
   LazyGrid lg{true, 0u, false};   // the grid starts empty (k_step)
   EnvConst<C> ec;   // n changes only in a reset
   ec.set(s.hdr);
-  // ROT: the step's request walk was made at the end of the previous step (kWalkRotate); the first
-  // step's here, and a reset's -- which replaces the request mask and sets `fresh` -- after it
-  constexpr bool ROT = kWalkRotate && POLICY == POL_GREEDY && !kAblationBuild;
+  // ROT: the greedy loop is rotated.  The request walk of step t + 1 (policy_walk: nine dependent LDS
+  // lookups) is issued right after step t's regeneration, and its results cross the back-edge in
+  // registers, so their latency is behind the loop branch instead of in front of the policy's distance
+  // tests.  The first step's walk is made here, and a reset's -- which replaces the request mask and
+  // sets `fresh` -- after it.
+  constexpr bool ROT = POLICY == POL_GREEDY && !kAblationBuild;
   [[maybe_unused]] uint32_t wrp[C::R], wtg[C::R];
   if constexpr (ROT) policy_walk<C>(s, L, wrp, wtg);
   for (int stp = 0; stp < a.steps; ++stp) {
@@ -240,13 +231,8 @@ __device__ __forceinline__ void run_steps_fast(const StepParams& a, Regs<C>& s, 
     uint4 rb = stream_block(k, gid, s.epi, (s.hdr + 1u) & 0xFFFFu, PUR_REGEN, 0u);
     asm volatile("" : "+v"(rb.x), "+v"(rb.y), "+v"(rb.z), "+v"(rb.w));
     float rew[C::NAM];
-    const bool done = step_env<C, false, false, POLICY != POL_GREEDY || kAblationBuild, true>(s, L, d, OrderIn{nullptr, 0, nullptr}, nullptr, nullptr, k, gid, e, C::NAM, PH_ALL,
-                                                (uint32_t)a.T, (uint32_t)a.W, rew, nullptr, tid, ablate, &lg,
-#ifndef WH_NO_ENV_CONST   // (A/B: n and the live masks recomputed from the header in every step)
-                                                &rb, &ec);
-#else
-                                                &rb);
-#endif
+    const bool done = step_env_fused<C, POLICY != POL_GREEDY || kAblationBuild>(s, L, d, k, gid, e, (uint32_t)a.T, (uint32_t)a.W, rew, tid,
+                                                                                 ablate, &lg, &rb, &ec);
     if constexpr (ROT) policy_walk<C, true>(s, L, wrp, wtg);   // the next step's (redone below after a reset)
     if (!(ablate & 64)) {
       store_row<C>(rrow + tid * C::NAM, rew);

@@ -125,8 +125,7 @@ __global__ __launch_bounds__(BT) void k_step_record(RecordParams p) {
       if (POLICY == POL_EXTERNAL) {
 #pragma unroll
         for (int i = 0; i < C::NAM; ++i) {
-          uint32_t act = i < na ? (uint32_t)a.actions[e * na + i] : 4u;
-          act = act > 8u ? 4u : act;   // (what move_of does with such a value)
+          const uint32_t act = valid_action(i < na ? (uint32_t)a.actions[e * na + i] : 4u);
           if (i < na) ract[i] = (uint8_t)act;
           d[i] = L.mv(act);
         }

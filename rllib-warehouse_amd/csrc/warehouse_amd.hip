@@ -503,11 +503,7 @@ static int resolve_step(const StepCall& c, void* stream, wh_launch* out) {
   if (k->step_fast[policy] && a.phase == PH_ALL && a.rewards && a.dones && !a.returns &&
       !a.stats.episode_return && !a.mask && !a.order && !a.regen && !a.n_inactive && a.autoreset &&
       c.g.NA == k->NAM && ((uintptr_t)a.rewards & ralign) == 0)
-#ifndef WH_NO_EPS0   // (A/B: the instance that tests p in every step for every launch)
     kern = (policy == POL_GREEDY && !(a.p > 0.0f)) ? k->step_fast_eps0 : k->step_fast[policy];   // (the kernel's own test of p)
-#else
-    kern = k->step_fast[policy];
-#endif
   const bool wide = c.lanes == WH_WIDE_LANES;   // k_step_wide (csrc/step_wide.h): 16 lanes per env
   out->kern = wide ? k->step_wide[policy] : kern;
   out->grid = wide ? grid_wide(c.B) : grid_for(c.B);

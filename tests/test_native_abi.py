@@ -49,7 +49,7 @@ def test_library_built_from_this_tree():
     assert {"Makefile", "version.cpp", "warehouse_amd.hip", "policy_mlp.hip", "philox.h", "abi_args.h", "warehouse_amd.h",
             # the kernel headers warehouse_amd.hip is made of, and the geometry both engines share
             "device_vocab.h", "reset.h", "policy.h", "step_env.h", "step_params.h", "step_wide.h", "step_loops.h",
-            "observe.h", "replay.h", "prio.h", "sampler.h", "pack.h", "geometry.h",
+            "observe.h", "replay.h", "prio.h", "sampler.h", "pack.h", "geometry.h", "step_record.h", "sac.h",
             # ... and the ones policy_mlp.hip is made of
             "mlp_common.h", "mlp32.h", "mlp16.h", "mlp_f32.h", "mlp_pack.h"} <= set(names)
 
