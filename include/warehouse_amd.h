@@ -317,7 +317,11 @@ int wh_mlp_pack_device(const wh_mlp_desc* d, const float* w0, const float* b0, c
 
 /* obs [rows, in_dim] f32 -> logits [rows, 9] f32 and/or actions [rows] int32 (either may be NULL,
  * not both).  explore = 0: argmax, first maximum wins; explore = 1: Gumbel-max sample of
- * Categorical(logits), noise from philox (seed; counter row, step, purpose 5). */
+ * Categorical(logits): the first maximum of logit[o] - log(-log u[o]), the noise from the philox
+ * contract, purpose 5: counter (row & 0xFFFFFFFF, row >> 32, step, 5 << 24 | block) keyed by seed
+ * (low word, high word), row the row's index in this launch, blocks 0-2; action o takes word o of the
+ * twelve (9-11 unused) as u = (float(w >> 8) + 0.5f) * 2^-24 in f32.  u lies in (0, 1]: the largest
+ * 24-bit draw rounds to exactly 1, whose noise is +inf, and that action is taken. */
 int wh_mlp_forward(const wh_mlp_desc* d, const void* packed, int64_t rows, const float* obs,
                    float* logits, int32_t* actions, int32_t explore, uint64_t seed, uint32_t step,
                    void* stream);

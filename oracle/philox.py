@@ -23,6 +23,17 @@ Streams (purpose, t):
   (pickup and target words interleave so the usual k <= 2 reopenings cost one Philox block)
   POLICY  (3, t_obs)  word 2i: coin u = (w >> 8) / 2**24, random iff u < p; word 2i+1: action uniform_int(9)
   RANDOM  (4, t_obs)  word i: action uniform_int(9)
+
+Three purposes take counters of their own (the key is the same):
+  MLP     5  ctr = (row & 0xffffffff, row >> 32, step, (5 << 24) | block), row the absolute row of the
+             launch, blocks 0-2.  word o (o < 9; words 9-11 unused): the Gumbel noise of action o,
+             u = (f32(w >> 8) + 0.5f) * 2**-24 in float32 -- (0, 1], exactly 1 for w >> 8 = 0xFFFFFF --
+             and action = first maximum of z_o - log(-log(u_o)) (modelled in oracle/policy_tail.py)
+  REPLAY  6  ctr = (sample m, draw & 0xffffffff, draw >> 32, 6 << 24), block 0 only.
+             word 0: slot = uniform_int(filled, .); word 1: env = uniform_int(B, .);
+             index = slot * B + env (wh_replay_gather with idx = NULL)
+  PRIO    7  ctr = (sample m, draw & 0xffffffff, draw >> 32, 7 << 24), block 0 only.
+             r = word 0 << 32 | word 1; mass = (r * total) >> 64 (wh_replay_prio_sample with u = NULL)
 """
 from __future__ import annotations
 
@@ -33,6 +44,7 @@ W0, W1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
 MASK32 = np.uint64(0xFFFFFFFF)
 
 RESET, REGEN, POLICY, RANDOM = 1, 2, 3, 4
+MLP = 5
 
 
 def philox4x32_10(c0, c1, c2, c3, k0, k1):

@@ -9,7 +9,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 
-constexpr uint32_t PUR_MLP = 5;         // philox purpose (1-4 are the simulator's, philox.h)
+constexpr uint32_t PUR_MLP = 5;         // philox purpose (1-4 are the simulator's, device_vocab.h)
 
 struct MlpArgs {
   const void* packed;
@@ -146,7 +146,11 @@ __device__ __forceinline__ void emit_row(const float (&z)[9], int64_t row, const
     float best = -INFINITY;
     int arg = 0;
     if (a.explore) {
-      // Gumbel-max: argmax(z + g), g = -log(-log u), u in (0,1) from philox(row, step)
+      // Gumbel-max: first maximum of z_o + g_o, g = -log(-log u).  Action o takes word o of philox
+      // blocks 0-2 of counter (row lo, row hi, step, PUR_MLP << 24 | block), key (seed lo, seed hi);
+      // words 9-11 are unused.  u = (f32(w >> 8) + 0.5f) * 2^-24 lies in (0, 1]: for w >> 8 = 0xFFFFFF
+      // the f32 sum rounds to 2^24, u = 1, g = +inf and that action is taken (once in 2^24 draws).
+      // Modelled by oracle/policy_tail.py.
       uint32_t u32[12];
 #pragma unroll
       for (int b = 0; b < 3; ++b) {
