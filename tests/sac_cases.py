@@ -21,8 +21,16 @@ import torch
 GUARD = 256
 L_LOGIT, QM = 4.0, 10.0
 REWARDS = np.array([-1.0, 0.0, 1.0, 10.0], np.float32)
-NAS = (1, 4, 9, 16)
+L_PEAKED = 60.0
+# A workgroup of k_sac_td owns floor(256 / NA) samples and stages its span of every [rows, 9] array
+# with an unaligned head of 0-3 floats that depends on its first row.  NA = 1, 4, 9 and 16 make a
+# span of 256, 256, 252 and 256 rows, a multiple of 16 bytes, so every block has the same head; NA =
+# 3, 5, 10 and 11 make spans of 255, 255, 250 and 253 rows, whose float counts are 3, 3, 2 and 1
+# mod 4, so the head changes from block to block through 1, 2 and 3.  NA = 2 and 8 (the headline's
+# agent count) take the 16 % NA == 0 shuffle sum.  (tests/test_sac_cpu.py checks this arithmetic.)
+NAS = (1, 2, 3, 4, 5, 8, 9, 10, 11, 16)
 MS = (1, 65, 300)
+BLOCK_ROWS = 256
 DISCOUNT = 0.99 ** 3
 EPS24 = 2.0 ** -24
 
@@ -108,7 +116,20 @@ def make_inputs(M, NA, seed):
     return inp
 
 
-# option cases: (name, twin target, q networks: 2 / 1 / 0, use n, mask_dones, alpha, byte offset of every array)
+def peaked_logits(rows, seed):
+    """pi_next of a near-deterministic trained policy: one logit of every row at +60 and the rest in
+    [-60, 0] (exp underflows to 0 where the distance exceeds 103, logp is near -120); with more than
+    one row, row 0 -- always live: n[0] = NA -- holds nine equal logits."""
+    rng = np.random.default_rng(seed)
+    pi = rng.uniform(-L_PEAKED, 0.0, (rows, 9)).astype(np.float32)
+    pi[np.arange(rows), rng.integers(0, 9, rows)] = L_PEAKED
+    if rows > 1:
+        pi[0] = L_PEAKED
+    return pi
+
+
+# option cases: (name, twin target, q networks: 2 / 1 / 0, use n, mask_dones, alpha, byte offset of every array
+# [, the bound L of |pi_next|: L_PEAKED takes peaked_logits])
 OPTIONS = (
     ("twin, n, no mask", True, 2, True, 0, 0.2, 0),
     ("twin, n = NULL, mask, alpha 0, offset 4", True, 2, False, 1, 0.0, 4),
@@ -116,6 +137,7 @@ OPTIONS = (
     ("single Q, twin target, offset 4", True, 1, True, 0, 0.2, 4),
     ("targets only, offset 4", True, 0, True, 0, 0.2, 4),
     ("targets only, single target, n = NULL, mask", False, 0, False, 1, 0.2, 0),
+    ("peaked policies, twin, n, no mask, offset 4", True, 2, True, 0, 0.2, 4, L_PEAKED),
 )
 
 
@@ -165,8 +187,12 @@ def case_td(nat, lib, device, NA, M, quarter=False):
     zeros where the contract states them.  Returns the largest errors seen, as fractions of the bounds."""
     inp0 = make_inputs(M, NA, 1000 * NA + M)
     worst = dict(y=0.0, td_rows=0.0, td=0.0)
-    for name, twin_t, nq, use_n, mask, alpha, offset in OPTIONS:
+    for name, twin_t, nq, use_n, mask, alpha, offset, *rest in OPTIONS:
+        L = rest[0] if rest else L_LOGIT
         inp = dict(inp0)
+        if L == L_PEAKED:
+            inp["pi_next"] = peaked_logits(M * NA, 1000 * NA + M)
+        assert float(np.abs(inp["pi_next"]).max()) <= L
         if not twin_t:
             inp["q2t_next"] = None
         if nq < 2:
@@ -181,12 +207,13 @@ def case_td(nat, lib, device, NA, M, quarter=False):
         got = run_td(nat, lib, device, M, NA, inp, alpha=alpha, discount=DISCOUNT, mask_dones=mask, offset=offset,
                      outputs=outputs)
         want = dict(zip(("y", "td_rows", "td"), model(inp, NA, alpha=alpha, discount=DISCOUNT, mask_dones=mask)))
-        by, btd = bounds(NA, alpha, np.float32(DISCOUNT))
+        by, btd = bounds(NA, alpha, np.float32(DISCOUNT), L=L)
         scale = 0.25 if quarter else 1.0
         for k in outputs:
             err = float(np.abs(got[k].astype(np.float64) - want[k]).max())
             b = btd if k == "td" else by
-            worst[k] = max(worst[k], err / b)
+            key = k if L == L_LOGIT else "peaked " + k
+            worst[key] = max(worst.get(key, 0.0), err / b)
             assert err <= scale * b, f"NA={NA} M={M} [{name}] {k}: error {err:.3e}, bound {scale * b:.3e}"
         # exact zeros: rows i >= n[m], everything of samples with n[m] <= 0
         n = np.full(M, NA) if inp["n"] is None else inp["n"]
@@ -203,16 +230,18 @@ def case_td(nat, lib, device, NA, M, quarter=False):
 def case_float32_model(NA, M):
     """The float32 numpy transcription of the formula stays under a quarter of the bounds on the
     test's own inputs (if it did not, the operation order would be wrong, not the bound)."""
-    inp = make_inputs(M, NA, 1000 * NA + M)
+    inp0 = make_inputs(M, NA, 1000 * NA + M)
     worst = dict(y=0.0, td_rows=0.0, td=0.0)
-    for alpha, mask in ((0.2, 0), (0.0, 1)):
+    for alpha, mask, L in ((0.2, 0, L_LOGIT), (0.0, 1, L_LOGIT), (0.2, 0, L_PEAKED)):
+        inp = inp0 if L == L_LOGIT else dict(inp0, pi_next=peaked_logits(M * NA, 1000 * NA + M))
         a = model(inp, NA, alpha=alpha, discount=DISCOUNT, mask_dones=mask, dtype=np.float32)
         b = model(inp, NA, alpha=alpha, discount=DISCOUNT, mask_dones=mask)
-        by, btd = bounds(NA, alpha, np.float32(DISCOUNT))
+        by, btd = bounds(NA, alpha, np.float32(DISCOUNT), L=L)
         for k, x, w, bound in zip(("y", "td_rows", "td"), a, b, (by, by, btd)):
             err = float(np.abs(x.astype(np.float64) - w).max())
-            worst[k] = max(worst[k], err / bound)
-            assert err <= 0.25 * bound, f"float32 model NA={NA} M={M} {k}: {err:.3e} > {0.25 * bound:.3e}"
+            key = k if L == L_LOGIT else "peaked " + k
+            worst[key] = max(worst.get(key, 0.0), err / bound)
+            assert err <= 0.25 * bound, f"float32 model NA={NA} M={M} L={L} {k}: {err:.3e} > {0.25 * bound:.3e}"
     return worst
 
 

@@ -13,6 +13,8 @@ Tolerances (stated here, checked below):
     |d| <= 1e-5 max|ref| per row (measured ~1e-7: f32 rounding in a different summation order), and
     argmax equal to the float64 reference's on EVERY row whose top-2 margin exceeds 1e-5 max|ref|
     (a closer pair is a tie at fp32 precision; the test reports how many such rows exist).
+These bounds let a single misplaced weight or a truncating rounding pass; tests/test_gpu_mlp_exact.py
+holds the same kernels to tolerance 0 on integer-valued networks, where exact answers exist.
 """
 import numpy as np
 import pytest

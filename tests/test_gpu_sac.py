@@ -4,7 +4,7 @@ within the bounds stated there, and warehouse.SACCritic end to end on a wrapped 
 tests/test_sac_cpu.py runs the wh_sac_td bodies on the host engine.
 
 Largest wh_sac_td errors seen on the device, as fractions of the bounds (y, td_rows, td):
-0.046, 0.051, 0.0107."""
+0.046, 0.051, 0.0107; on the peaked-policy case 0.031, 0.025, 0.0053."""
 import ctypes
 import os
 import subprocess

@@ -5,7 +5,9 @@ tests/test_sac_refusals.py.)
 
 The host engine and the float32 numpy model must stay under a QUARTER of the stated bounds on the
 test's own inputs.  Largest errors seen, as fractions of the full bounds (y, td_rows, td): float32
-model 0.046, 0.051, 0.0096; host engine 0.046, 0.051, 0.0107."""
+model 0.046, 0.051, 0.0115; host engine 0.046, 0.051, 0.0107; on the peaked-policy case (logits up
+to +-60, the bound formula with L = 60) float32 model 0.030, 0.022, 0.0053, host engine 0.033, 0.025,
+0.0053."""
 import os
 import subprocess
 import sys
@@ -36,6 +38,40 @@ def test_td_on_the_host_engine_against_the_float64_model(nat, NA, M):
 def test_float32_model_stays_under_a_quarter_of_the_bounds(NA, M):
     worst = sc.case_float32_model(NA, M)
     print("float32 model NA", NA, "M", M, "errors / bounds", worst)
+
+
+def test_agent_counts_reach_every_staging_head_and_both_td_sums():
+    """The arithmetic behind sac_cases.NAS: which unaligned heads (floats up to the next 16-byte
+    boundary) the blocks of k_sac_td meet at M = 300, from a 16-byte aligned array and from one 4 bytes
+    off, and how many blocks there are."""
+    heads, blocks = {}, {}
+    for NA in sc.NAS:
+        spw = sc.BLOCK_ROWS // NA
+        blocks[NA] = -(-300 // spw)
+        first = [b * spw * NA * 9 for b in range(blocks[NA])]        # a block's first float of a [rows, 9] array
+        heads[NA] = [sorted({(4 - (f + off) % 4) % 4 for f in first}) for off in (0, 1)]
+    assert all(blocks[NA] >= 4 for NA in sc.NAS if NA >= 3), blocks
+    for NA in (1, 2, 4, 8, 9, 16):                                   # spans of whole 16-byte pieces: one head
+        assert heads[NA] == [[0], [3]], (NA, heads[NA])
+    for NA in (3, 5, 10, 11):                                        # the head changes from block to block
+        assert len(heads[NA][0]) >= 2 and len(heads[NA][1]) >= 2, (NA, heads[NA])
+    assert {h for NA in (3, 5, 10, 11) for hs in heads[NA] for h in hs} == {0, 1, 2, 3}
+    assert [(sc.BLOCK_ROWS // NA) * NA * 9 % 4 for NA in (3, 5, 10, 11)] == [3, 3, 2, 1]
+    assert {NA for NA in sc.NAS if 16 % NA == 0} == {1, 2, 4, 8, 16} and {3, 5, 9, 10, 11} <= set(sc.NAS)
+    assert set(sc.MS) == {1, 65, 300}
+
+
+def test_peaked_logits_are_what_the_case_states():
+    import numpy as np
+
+    pi = sc.peaked_logits(300, 7)
+    assert pi.dtype == np.float32 and np.abs(pi).max() == sc.L_PEAKED
+    assert (pi[0] == sc.L_PEAKED).all()                              # the row of nine equal logits
+    rest = np.sort(pi[1:], axis=1)
+    assert (rest[:, -1] == sc.L_PEAKED).all() and (rest[:, :-1] <= 0).all() and (rest[:, :-1] >= -sc.L_PEAKED).all()
+    assert len(set(pi[1:].argmax(axis=1))) == 9
+    assert (np.exp(np.float32(-120.0)) == 0) and (rest[:, -1] - rest[:, 0]).max() > 110     # exp underflows on some
+    assert len([o for o in sc.OPTIONS if len(o) == 8 and o[7] == sc.L_PEAKED]) == 1
 
 
 def test_model_on_a_hand_worked_row():
