@@ -360,6 +360,50 @@ typedef struct wh_mlp_job {
 } wh_mlp_job;
 int wh_mlp_forward_multi(const wh_mlp_desc* d, int32_t njobs, const wh_mlp_job* jobs, void* stream);
 
+/* MLP TRAINING: the same three-layer ReLU network's training forward and backward in exact f32
+ * (csrc/mlp_train.h), for a learner that keeps its master weights on the card.  Both read the f32
+ * parameters in torch nn.Linear layout (w0 [hidden0, in_dim], b0 [hidden0], w1 [hidden1, hidden0],
+ * b1 [hidden1], w2 [9, hidden1], b2 [9]) straight from device memory: no blob.  Device only.
+ *
+ * wh_mlp_train_forward, all row-major f32, every dot product an f32 fma chain (v_mfma_f32_32x32x2_f32):
+ *   h0 [rows, hidden0] = max(W0 x + b0, 0),  h1 [rows, hidden1] = max(W1 h0 + b1, 0),
+ *   logits [rows, 9] = W2 h1 + b2.
+ * The values equal a float32 reference up to summation order.  The bias is added after the sum here and
+ * the k order differs from wh_mlp_forward's, so on real-valued weights the logits need NOT be bit-equal
+ * to wh_mlp_forward's WH_MLP_F32 logits (on integer-valued networks whose sums are exact, they are).
+ *
+ * wh_mlp_backward, with dZ = dlogits [rows, 9] and h0 / h1 as the forward wrote them:
+ *   gW2 = dZ^T h1            gb2 = sum_r dZ       dH1 = (dZ W2)  . [h1 > 0]
+ *   gW1 = dH1^T h0           gb1 = sum_r dH1      dH0 = (dH1 W1) . [h0 > 0]
+ *   gW0 = dH0^T x            gb0 = sum_r dH0
+ * The mask is h > 0: a unit whose pre-activation is exactly 0 passes no gradient (torch's relu backward).
+ * The six gradients, in the parameters' layouts, are OVERWRITTEN, not accumulated (torch accumulates
+ * .grad itself); no gradient w.r.t. obs is produced.  No floating-point atomics: every gradient element
+ * is summed in an order fixed by the shape and `rows` alone, so two calls on the same inputs agree bit
+ * for bit.  `work` is scratch (dH1, dH0 and, above 512 rows, the partial weight gradients of up to 16
+ * row slices, which a second pass adds in slice order); its layout is the kernels' own, its size
+ * wh_mlp_train_query's `work_bytes` (never 0), and it is 16-byte aligned.  Neither entry point
+ * allocates or synchronises: both only enqueue on `stream` (three launches forward; three backward,
+ * four above 512 rows).
+ *
+ * Checked in this order before anything is launched (a refused call launches and writes nothing):
+ * d == NULL WH_EINVAL; a shape that is no variant's, or out_dim != 9, WH_ENOTSUP; precision other than
+ * WH_MLP_F32 WH_ENOTSUP (the backward takes f32 operands only); rows < 0 WH_EINVAL; NULL among w and
+ * its six pointers, obs, h0, h1, logits (forward) or dlogits (backward), g and its six pointers, work
+ * WH_EINVAL; work not 16-byte aligned WH_EINVAL; rows > WH_MLP_TRAIN_MAX_ROWS, the largest the launch
+ * geometry is stated for, WH_EINVAL.  rows == 0 is WH_OK: the forward launches nothing, the backward
+ * writes zeros to all six gradients.  wh_mlp_train_query applies the rules of d and rows; work_bytes
+ * may be NULL. */
+#define WH_MLP_TRAIN_MAX_ROWS 16777216 /* 2^24 */
+typedef struct wh_mlp_weights { const float *w0, *b0, *w1, *b1, *w2, *b2; } wh_mlp_weights; /* device, nn.Linear layout */
+typedef struct wh_mlp_grads { float *w0, *b0, *w1, *b1, *w2, *b2; } wh_mlp_grads;           /* same shapes */
+int wh_mlp_train_query(const wh_mlp_desc* d, int64_t rows, int64_t* work_bytes);
+int wh_mlp_train_forward(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows, const float* obs,
+                         float* h0, float* h1, float* logits, void* stream);
+int wh_mlp_backward(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows, const float* obs,
+                    const float* h0, const float* h1, const float* dlogits, const wh_mlp_grads* g,
+                    void* work, void* stream);
+
 /* REPLAY RING: off-policy transitions kept as packed states instead of observation rows (every row
  * is a function of the packed state: 265 bytes per Medium-8 transition against 5,289 as f32 rows).
  * A ring holds `capacity` slots; a slot is one time step of all B envs.  The buffers are device

@@ -403,6 +403,54 @@ inline int sac_td_call(int64_t M, int32_t NA, const wh_sac_td_args* a) {
   return (a->mask_dones != 0 && !a->dones) ? WH_EINVAL : WH_OK;
 }
 
+// ----------------------------------------------------------------------------- MLP training
+// wh_mlp_train_query / wh_mlp_train_forward / wh_mlp_backward, in the header's order: the desc, its
+// shape, its precision, rows < 0, the pointers, the alignment of `work`, the empty batch, the row limit.
+inline bool mlp_train_shape_ok(const wh_mlp_desc* d) {
+  const int32_t shapes[3][3] = {{37, 256, 256}, {82, 512, 512}, {145, 1024, 256}};   // Small, Medium, Large
+  for (const auto& s : shapes)
+    if (d->in_dim == s[0] && d->hidden0 == s[1] && d->hidden1 == s[2]) return d->out_dim == 9;
+  return false;
+}
+
+inline int mlp_train_desc(const wh_mlp_desc* d, int64_t rows) {
+  if (!d) return WH_EINVAL;
+  if (!mlp_train_shape_ok(d) || d->precision != WH_MLP_F32) return WH_ENOTSUP;
+  return rows < 0 ? WH_EINVAL : WH_OK;
+}
+
+inline bool mlp_weights_ok(const wh_mlp_weights* w) { return w && w->w0 && w->b0 && w->w1 && w->b1 && w->w2 && w->b2; }
+inline bool mlp_grads_ok(const wh_mlp_grads* g) { return g && g->w0 && g->b0 && g->w1 && g->b1 && g->w2 && g->b2; }
+
+inline int mlp_train_query_call(const wh_mlp_desc* d, int64_t rows) {
+  const int rc = mlp_train_desc(d, rows);
+  if (rc) return rc;
+  return rows > WH_MLP_TRAIN_MAX_ROWS ? WH_EINVAL : WH_OK;
+}
+
+// *live = 0: WH_OK with nothing to launch (rows == 0)
+inline int mlp_train_forward_call(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows, const float* obs,
+                                  const float* h0, const float* h1, const float* logits, bool* live) {
+  *live = false;
+  const int rc = mlp_train_desc(d, rows);
+  if (rc) return rc;
+  if (!mlp_weights_ok(w) || !obs || !h0 || !h1 || !logits) return WH_EINVAL;
+  if (rows > WH_MLP_TRAIN_MAX_ROWS) return WH_EINVAL;
+  *live = rows > 0;
+  return WH_OK;
+}
+
+// (rows == 0 is live: the six gradients are written, as zeros)
+inline int mlp_backward_call(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows, const float* obs,
+                             const float* h0, const float* h1, const float* dlogits, const wh_mlp_grads* g,
+                             const void* work) {
+  const int rc = mlp_train_desc(d, rows);
+  if (rc) return rc;
+  if (!mlp_weights_ok(w) || !obs || !h0 || !h1 || !dlogits || !mlp_grads_ok(g) || !work) return WH_EINVAL;
+  if ((uintptr_t)work % 16 != 0) return WH_EINVAL;
+  return rows > WH_MLP_TRAIN_MAX_ROWS ? WH_EINVAL : WH_OK;
+}
+
 // the quantisation rule, one for both engines (plain C++: also device code)
 #if defined(__HIPCC__)
 __host__ __device__

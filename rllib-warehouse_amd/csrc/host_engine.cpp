@@ -994,6 +994,11 @@ int wh_mlp_forward(const wh_mlp_desc*, const void*, int64_t, const float*, float
 int wh_mlp_forward_x(const wh_mlp_desc*, const void*, int64_t, const void*, float*, int32_t*, int32_t, uint64_t,
                      uint32_t, void*) { return WH_ENOTSUP; }
 int wh_mlp_forward_multi(const wh_mlp_desc*, int32_t, const wh_mlp_job*, void*) { return WH_ENOTSUP; }
+int wh_mlp_train_query(const wh_mlp_desc*, int64_t, int64_t*) { return WH_ENOTSUP; }
+int wh_mlp_train_forward(const wh_mlp_desc*, const wh_mlp_weights*, int64_t, const float*, float*, float*, float*,
+                         void*) { return WH_ENOTSUP; }
+int wh_mlp_backward(const wh_mlp_desc*, const wh_mlp_weights*, int64_t, const float*, const float*, const float*,
+                    const float*, const wh_mlp_grads*, void*, void*) { return WH_ENOTSUP; }
 int wh_check_read(uint64_t*, int32_t) { return WH_ENOTSUP; }
 int wh_step_wide(const wh_config*, int64_t, uint32_t*, const int32_t*, float*, uint8_t*, const int32_t*, int32_t*,
                  uint64_t, int64_t, int32_t, void*) { return WH_ENOTSUP; }

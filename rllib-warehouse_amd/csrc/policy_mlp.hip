@@ -34,6 +34,7 @@
 #include <utility>
 #include <vector>
 
+#include "abi_args.h"
 #include "mlp_grid.h"
 #include "philox.h"
 #include "warehouse_amd.h"
@@ -47,6 +48,7 @@ int hip_rc(hipError_t e) { return e == hipSuccess ? WH_OK : WH_EHIP + (int)e; }
 #include "mlp16.h"        // Net16, k_mlp16: bf16 on 16x16x32 tiles
 #include "mlp_f32.h"      // NetF, k_mlp_f32: exact f32
 #include "mlp_pack.h"     // the three blob formats, the host packer and the device packer (k_mlp_pack)
+#include "mlp_train.h"    // the training forward and the backward on raw nn.Linear weights (k_train*)
 
 struct MlpKernel {
   int in, h0, h1, precision;
@@ -256,6 +258,30 @@ int wh_mlp_forward_multi(const wh_mlp_desc* d, int32_t njobs, const wh_mlp_job* 
   if (!mlp_grid::persistent(n, work, cus < n ? n : cus, m.first)) return WH_EINVAL;
   hipLaunchKernelGGL(k->fwd_multi, dim3((unsigned)m.first[n]), dim3(k->threads), 0, (hipStream_t)stream, m);
   return hip_rc(hipGetLastError());
+}
+
+// MLP TRAINING (csrc/mlp_train.h): the argument rules are abi_args.h's, the launches mlp_train.h's
+int wh_mlp_train_query(const wh_mlp_desc* d, int64_t rows, int64_t* work_bytes) {
+  if (const int rc = wh_abi::mlp_train_query_call(d, rows)) return rc;
+  if (work_bytes) *work_bytes = train::work_bytes(train::Dims{d->in_dim, d->hidden0, d->hidden1}, rows);
+  return WH_OK;
+}
+
+int wh_mlp_train_forward(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows, const float* obs,
+                         float* h0, float* h1, float* logits, void* stream) {
+  bool live;
+  if (const int rc = wh_abi::mlp_train_forward_call(d, w, rows, obs, h0, h1, logits, &live)) return rc;
+  if (!live) return WH_OK;
+  return train::forward(train::Dims{d->in_dim, d->hidden0, d->hidden1}, *w, rows, obs, h0, h1, logits,
+                        (hipStream_t)stream);
+}
+
+int wh_mlp_backward(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows, const float* obs,
+                    const float* h0, const float* h1, const float* dlogits, const wh_mlp_grads* g,
+                    void* work, void* stream) {
+  if (const int rc = wh_abi::mlp_backward_call(d, w, rows, obs, h0, h1, dlogits, g, work)) return rc;
+  return train::backward(train::Dims{d->in_dim, d->hidden0, d->hidden1}, *w, rows, obs, h0, h1, dlogits, *g, work,
+                         (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -48,7 +48,8 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_step_wide", "wh_rollout_wide", "wh_vector_step_wide",
            "wh_replay_put", "wh_replay_gather", "wh_replay_record",
            "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample",
-           "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi")
+           "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi",
+           "wh_mlp_train_query", "wh_mlp_train_forward", "wh_mlp_backward")
 
 WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
 WH_PRIO_MAX = 0x7FFFFFFF       # the largest stored priority
@@ -128,6 +129,16 @@ class WhMlpJob(ctypes.Structure):
     _fields_ = [("packed", ctypes.c_void_p), ("rows", ctypes.c_int64), ("obs", ctypes.c_void_p),
                 ("xfrag", ctypes.c_void_p), ("logits", ctypes.c_void_p), ("actions", ctypes.c_void_p),
                 ("explore", ctypes.c_int32), ("step", ctypes.c_uint32), ("seed", ctypes.c_uint64)]
+
+
+WH_MLP_TRAIN_MAX_ROWS = 1 << 24   # the largest `rows` of wh_mlp_train_forward / wh_mlp_backward
+
+
+class WhMlpWeights(ctypes.Structure):   # wh_mlp_weights and wh_mlp_grads: six device pointers, nn.Linear layout
+    _fields_ = [(k, ctypes.c_void_p) for k in ("w0", "b0", "w1", "b1", "w2", "b2")]
+
+
+WhMlpGrads = WhMlpWeights
 
 
 class WhSacTdArgs(ctypes.Structure):
@@ -229,6 +240,10 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_mlp_forward.argtypes = [_MD, _P, _I64, _P, _P, _P, _I32, _U64, ctypes.c_uint32, _P]
     S.wh_mlp_forward_x.argtypes = [_MD, _P, _I64, _P, _P, _P, _I32, _U64, ctypes.c_uint32, _P]
     S.wh_mlp_forward_multi.argtypes = [_MD, _I32, ctypes.POINTER(WhMlpJob), _P]
+    _MW = ctypes.POINTER(WhMlpWeights)
+    S.wh_mlp_train_query.argtypes = [_MD, _I64, ctypes.POINTER(ctypes.c_int64)]
+    S.wh_mlp_train_forward.argtypes = [_MD, _MW, _I64, _P, _P, _P, _P, _P]
+    S.wh_mlp_backward.argtypes = [_MD, _MW, _I64, _P, _P, _P, _P, _MW, _P, _P]
     S.wh_check_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), _I32]
     S.wh_rollout_prepare.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _P,
                                      ctypes.POINTER(ctypes.c_void_p)]
