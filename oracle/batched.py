@@ -270,7 +270,9 @@ def step(L: Layout, S: BState, actions: np.ndarray, draws, order: Optional[np.nd
 
 # --------------------------------------------------------------------------- observation
 def observe(L: Layout, S: BState) -> np.ndarray:
-    """[B, NA, 9R+1] int32 rows in sorted-key order; slots >= n are zero rows."""
+    """[B, NA, 9R+1] int32 rows in sorted-key order; slots >= n are zero rows.  A state with fewer
+    than R open requests (no reset or step leaves one; a caller can pack one) has zero request rows
+    after its open ones, as k_observe and the host engine define them."""
     B, NA, R = S.B, S.NA, L.R
     pk, dl, cell, valid = tables(L)
     null = L.null
@@ -289,6 +291,7 @@ def observe(L: Layout, S: BState) -> np.ndarray:
     order = np.argsort(S.pk_tgt < 0, axis=1, kind="stable")[:, :R]
     act_t = np.take_along_axis(S.pk_tgt, order, 1)
     req = np.concatenate([pk[order], dl[np.maximum(act_t, 0)]], axis=2)
+    req = np.where((act_t >= 0)[..., None], req, 0)
     out = np.zeros((B, NA, L.obs_len), np.int32)
     rows_all = np.arange(R)
     for i in range(NA):

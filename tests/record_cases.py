@@ -6,7 +6,10 @@ feature is defined as bit-equality with the five-launch route (put, step without
 reset, observe), which the oracle already pins, so every comparison is at tolerance 0.  Shapes:
 B = 300 -- one full workgroup of 256 envs and one of 44, so records past env 256 and lanes past B are
 both exercised -- and B = 37 for one variant; capacity 5 and 9 recorded steps, so the ring wraps; envs
-placed at T-3, T-2, T-1 and T-8, so every env ends an episode within the 9 steps.
+placed at T-3, T-2, T-1 and T-8, so every env ends an episode within the 9 steps.  The *_fuzzed cases
+start from fuzz_states.place_fuzzed (requests about to expire at any t, sparse tables, clocks from 0
+to T) and hold collect to the oracle's rollout as well; their clocks make envs end an episode early
+in a multi-step launch, so the launch goes on stepping envs it has reset itself.
 """
 import ctypes
 
@@ -14,8 +17,11 @@ import numpy as np
 import torch
 
 import replay_cases as rc
+from fuzz_states import bstate, canonical, draw_for, place_fuzzed
+from oracle import batched as ob
+from oracle import core as oc
 from replay_cases import CAP, GUARD, SEED, STEPS, place_near_end
-from wide_cases import canon
+from wide_cases import Bins, assert_same as assert_oracle_state, canon, oracle_rollout
 
 NB = 300
 RING = ("states", "actions", "rewards", "dones")
@@ -38,14 +44,15 @@ def guard_ring(buf):
     return raw
 
 
-def twins(make, variant, nb, na, train, **fused):
+def twins(make, variant, nb, na, train, place=None, **fused):
     """Two envs with one seed and one state, each with episode stats and a guarded buffer: the first
-    recorded by the record launch, the second by the five launches."""
+    recorded by the record launch, the second by the five launches.  `place(env)` puts a fresh env
+    into its first state (default place_near_end)."""
     import warehouse
 
     envs = [make(variant, nb, na, train=train, seed=SEED) for _ in range(2)]
     for e in envs:
-        place_near_end(e)
+        (place or place_near_end)(e)
         e.enable_episode_stats()
     assert torch.equal(envs[0].state.cpu(), envs[1].state.cpu())
     bufs = [warehouse.ReplayBuffer(envs[0], CAP, fused=True, **fused),
@@ -95,13 +102,52 @@ def case_ring_equal(make, variant, na, train, nb=NB):
         assert len(n_seen) > 1
 
 
+# ----------------------------------------------------------------------------- 1b. ring equality, fuzzed
+RING_FUZZ_SEED, COLLECT_FUZZ_SEED = 211, 223   # place_fuzzed draws of the two fuzzed cases below
+
+
+def case_ring_equal_fuzzed(make, variant, na, train, full, nb=NB):
+    """case_ring_equal from fuzz_states.place_fuzzed: 9 steps of step(fused=True) against
+    step(fused=False), everything equal after every step.  full=True: greedy 0.3 actions; full=False:
+    sparse request tables and seeded uniform actions.  Requests must expire inside recorded steps
+    (also at t < W, where no episode holds one about to) and envs must be stepped again after a done."""
+    envs, bufs, raws = twins(make, variant, nb, na, train, place=lambda e: place_fuzzed(e, full, RING_FUZZ_SEED))
+    rng = np.random.default_rng(RING_FUZZ_SEED)
+    R, W = envs[0].R, envs[0].geometry["W"]
+    was_done = np.zeros(nb, bool)
+    cov = dict(expired=0, expired_below_w=0, again=0, sparse=0)
+    for s in range(STEPS):
+        pre = canon(envs[1])
+        if full:
+            acts = envs[1].policy("greedy", 0.3).clone()
+        else:
+            acts = torch.as_tensor(rng.integers(0, 9, (nb, envs[1].agent_slots)).astype(np.int32)).to(envs[1].device)
+        a, b = bufs[0].step(acts), bufs[1].step(acts)
+        assert bufs[0].last_fused is True and bufs[1].last_fused is False
+        for x, y, what in zip(a, b, ("obs", "rewards", "dones")):
+            assert torch.equal(x.cpu(), y.cpu()), f"{what} differ at step {s}"
+        assert_same(envs, bufs, raws, f"{variant}/{na} full={full} step {s}")
+        opened = pre["pickup_target"] >= 0
+        last = opened & (pre["pickup_timer"] == 1)            # expiry comes before the pickups: all of them go
+        cov["expired"] += int(last.sum())
+        cov["expired_below_w"] += int((last & (pre["t"] < W - 1)[:, None]).sum())
+        cov["sparse"] += int((opened.sum(1) < R).sum())
+        cov["again"] += int(was_done.sum())
+        was_done |= b[2].cpu().numpy().astype(bool)
+    print(f"coverage {variant}/{na} train={train} full={full}: {cov}")
+    assert cov["expired"] >= 1 and cov["expired_below_w"] >= 1 and cov["again"] >= 1, cov
+    assert (cov["sparse"] == 0) if full else (cov["sparse"] >= 1), cov
+    return cov
+
+
 # ----------------------------------------------------------------------------- 2. collect
-def case_collect_equal(make, variant, na, train, policy, p, prioritized=False):
+def case_collect_equal(make, variant, na, train, policy, p, prioritized=False, place=None):
     """collect(K, policy, p) against K x [env.policy -> five-launch step], K = 1, 3 and 5 (= capacity)
     from cursor 3, so that K = 3 and K = 5 wrap: returned rows, rewards [K,B,NA], dones [K,B], ring,
-    state, stats; with `prioritized`, the tree's leaves, sums and max_q."""
+    state, stats; with `prioritized`, the tree's leaves, sums and max_q.  Returns the dones [K,B] of
+    the K = 5 launch."""
     for K in (1, 3, CAP):
-        envs, bufs, raws = twins(make, variant, NB, na, train, prioritized=prioritized)
+        envs, bufs, raws = twins(make, variant, NB, na, train, place=place, prioritized=prioritized)
         for s in range(3):
             acts = envs[1].policy("greedy", 0.3).clone()
             bufs[0].step(acts), bufs[1].step(acts)
@@ -112,6 +158,7 @@ def case_collect_equal(make, variant, na, train, policy, p, prioritized=False):
         obs, rew, done = bufs[0].collect(K, policy, p)
         assert bufs[0].last_fused is True
         assert rew.shape == (K, NB, envs[0].agent_slots) and done.shape == (K, NB)
+        launch_dones = done.cpu().numpy().astype(bool)
         for k in range(K):
             o, r, d = bufs[1].step(envs[1].policy(policy, p))
             assert torch.equal(rew[k].cpu(), r.cpu()), f"K={K}: rewards of step {k}"
@@ -131,6 +178,83 @@ def case_collect_equal(make, variant, na, train, policy, p, prioritized=False):
     assert_same(envs, bufs, raws, "collect fallback")
     cur = bufs[0].cursor
     assert bufs[0].collect(0, policy, p)[1].shape[0] == 0 and bufs[0].cursor == cur
+    return launch_dones
+
+
+def steps_after_reset(dones):
+    """Env-steps of a launch taken after the launch reset that env: dones [K, B] of its steps."""
+    d = np.asarray(dones).astype(bool)
+    return int((np.cumsum(d, axis=0) - d > 0).sum())
+
+
+def case_collect_steps_on_after_resets(make):
+    """case_collect_equal from clocks T-5, T-4, T-6 and T-9: after the three single steps the envs sit
+    at T-2, T-1, T-3 and T-6, so collect(5) resets three quarters of them at its steps 1, 0 and 2 and
+    goes on stepping them -- the reachable twin of case_collect_fuzzed's states."""
+    lead = (5, 4, 6, 9)
+    dones = case_collect_equal(make, "medium", 8, False, "greedy", 0.3, place=lambda e: place_near_end(e, lead=lead))
+    for g, first in enumerate((1, 0, 2, None)):
+        col = dones[:, g::4]
+        assert (col.any(0) == (first is not None)).all()
+        if first is not None:
+            assert col[first].all() and col.sum() == col.shape[1]
+    assert steps_after_reset(dones) == NB // 4 * (3 + 4 + 2)
+
+
+# ----------------------------------------------------------------------------- 2b. collect, fuzzed
+def case_collect_fuzzed(make, variant, na, train, policy, p, prioritized=False):
+    """From place_fuzzed(full=True): three single steps (cursor 3), then collect(5, policy, p), against
+    5 x [env.policy -> five-launch step] as case_collect_equal does AND against the oracle's rollout
+    under the same philox contract: rewards and dones of every step, and at the end the rows, the
+    canonical state and the episode-stat bins.  The three single steps take every env placed at
+    T-3 .. T across its episode end, so the envs are placed again (a second draw) before the launch:
+    its clocks T-3 .. T make the launch reset envs at its steps 2, 1, 0 and 0 and go on stepping them,
+    at least 100 such env-steps.  The stats keep running across the second placement."""
+    K, drawn = CAP, []
+    envs, bufs, raws = twins(make, variant, NB, na, train, prioritized=prioritized,
+                             place=lambda e: drawn.append(place_fuzzed(e, True, COLLECT_FUZZ_SEED)))
+    L, slots = oc.layout_for(variant), envs[0].agent_slots
+    S, d = bstate(*drawn[0]), ob.PhiloxDraws(SEED, np.arange(NB))
+    bins, epret = Bins(slots), np.zeros(NB, np.int64)
+    nmax = slots if train else None
+    rew3, dn3 = np.zeros((3, NB, slots), np.float32), np.zeros((3, NB), bool)
+    for s in range(3):
+        acts = envs[1].policy("greedy", 0.3).clone()
+        bufs[0].step(acts)
+        _, r, dn = bufs[1].step(acts)
+        rew3[s], dn3[s] = r.cpu().numpy(), dn.cpu().numpy().astype(bool)
+    oracle_rollout(L, S, d, 3, "greedy", 0.3, nmax, rew3, dn3, bins, epret)
+    assert_oracle_state(canon(envs[0]), S, "after the single steps")
+    for e in envs:
+        e.from_canonical(canonical(*draw_for(e, True, COLLECT_FUZZ_SEED + 1)))
+    S = bstate(*draw_for(envs[0], True, COLLECT_FUZZ_SEED + 1))
+    if prioritized:
+        for b in bufs:
+            b.update_priorities(np.arange(0, 2 * NB, 7), np.linspace(0.5, 9.0, len(np.arange(0, 2 * NB, 7))))
+    assert bufs[0].cursor == 3
+    obs, rew, done = bufs[0].collect(K, policy, p)
+    assert bufs[0].last_fused is True
+    for k in range(K):
+        o, r, dn = bufs[1].step(envs[1].policy(policy, p))
+        assert torch.equal(rew[k].cpu(), r.cpu()), f"rewards of step {k}"
+        assert torch.equal(done[k].cpu(), dn.cpu()), f"dones of step {k}"
+    assert torch.equal(obs.cpu(), o.cpu()), "rows of the final state"
+    assert_same(envs, bufs, raws, f"{variant}/{na} {policy} {p} fuzzed")
+    assert bufs[0].cursor == (3 + K) % CAP and bufs[0].filled == CAP
+    if prioritized:
+        for name in ("prio_leaf", "prio_node", "prio_max_q"):
+            assert torch.equal(getattr(bufs[0], name).cpu(), getattr(bufs[1], name).cpu()), name
+        assert int(bufs[0].prio_max_q) > 1 << 20
+    dones = done.cpu().numpy().astype(bool)
+    oracle_rollout(L, S, d, K, policy, p, nmax, rew.cpu().numpy(), dones, bins, epret)
+    assert_oracle_state(canon(envs[0]), S, "after collect")
+    np.testing.assert_array_equal(obs.cpu().numpy(), ob.observe(L, S))
+    bins.check(envs[0].stats)
+    np.testing.assert_array_equal(envs[0].stats.episode_return.cpu().numpy(), epret)
+    again = steps_after_reset(dones)
+    print(f"coverage {variant}/{na} train={train} {policy} {p}: steps after an in-launch reset {again}")
+    assert again >= 100, again
+    return again
 
 
 # ----------------------------------------------------------------------------- 3. sample after record
@@ -178,13 +302,22 @@ def case_fragments(make, variant, na):
     assert bufs[0].step(acts, operand="fragments", observe=False)[0] is None
     bufs[1].step(acts, observe=False)
 
+    policy_collect_equal(make, variant, na, 6)
+
+
+def policy_collect_equal(make, variant, na, K, place=None):
+    """warehouse.policy_collect (bf16 and f32 network) against policy_rollout with a recorder that does
+    the five launches by hand: ring, state, stats, returned operand and the ring's actions.  Returns
+    the dones [K, B] of the last network's trajectory."""
+    import warehouse
+
     for precision in ("bf16", "f32"):
         net = warehouse.policy.MLPPolicy(variant, seed=21, precision=precision)
-        envs, bufs, raws = twins(make, variant, NB, na, False)
+        envs, bufs, raws = twins(make, variant, NB, na, False, place=place)
         roll = make(variant, NB, na, seed=SEED)                  # policy_rollout's own env
-        place_near_end(roll)
+        (place or place_near_end)(roll)
         roll.enable_episode_stats()
-        seen = []
+        seen, dones = [], []
 
         def record(s, acts, rew, done):
             e, b = envs[1], bufs[1]
@@ -195,14 +328,23 @@ def case_fragments(make, variant, na):
             b.advance()
             assert torch.equal(rew, e.rewards) and torch.equal(done, e.dones)
             seen.append(acts.clone())
+            dones.append(done.cpu().numpy().astype(bool))
 
-        last = warehouse.policy.policy_rollout(roll, net, 6, explore=True, seed=9, first_step=4, record=record)
-        got = warehouse.policy_collect(bufs[0], net, 6, explore=True, seed=9, first_step=4)
+        last = warehouse.policy.policy_rollout(roll, net, K, explore=True, seed=9, first_step=4, record=record)
+        got = warehouse.policy_collect(bufs[0], net, K, explore=True, seed=9, first_step=4)
         assert torch.equal(got, last) and bufs[0].last_fused is True
         assert_same(envs, bufs, raws, f"policy_collect {precision}")
         assert torch.equal(envs[0].state, roll.state)
-        for s in range(6 - CAP, 6):                              # the ring's actions are the network's
+        for s in range(max(K - CAP, 0), K):                      # the ring's actions are the network's
             assert torch.equal(bufs[0].actions[s % CAP].to(torch.int32), seen[s]), f"actions of step {s}"
+    return np.stack(dones)
+
+
+def case_policy_collect_fuzzed(make, variant, na):
+    """policy_collect from place_fuzzed(full=True), K = 5: the ring byte-equal to policy_rollout with
+    the five-launch recorder, with envs stepped on after their reset."""
+    dones = policy_collect_equal(make, variant, na, CAP, place=lambda e: place_fuzzed(e, True, COLLECT_FUZZ_SEED))
+    assert steps_after_reset(dones) >= 100
 
 
 # ----------------------------------------------------------------------------- 5. refusals

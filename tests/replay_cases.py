@@ -6,7 +6,9 @@ host engine.  Every comparison is at tolerance 0: rows are byte values as floats
 integer or copied.  Shapes throughout: B = 37 envs (no multiple of a workgroup's 4 / 16 / 64 samples,
 of a wave or of the put kernel's 256 envs), capacity 5, 9 recorded steps, so the ring wraps.  Envs
 start at t = T-3 .. T-1 (and a fourth group at T-8), so different envs end their episode at
-different recorded steps, before and after the wrap.
+different recorded steps, before and after the wrap.  The *_fuzzed cases start from
+fuzz_states.place_fuzzed instead: request timers anywhere in 1 .. W (three in ten at 1, also at
+t < W), sparse request tables, crowded agents, clocks at 0, 5, 57, 150 and T-3 .. T.
 """
 import ctypes
 
@@ -16,6 +18,7 @@ import torch
 from oracle import batched as ob
 from oracle import core as oc
 from oracle import philox as oph
+from fuzz_states import place_fuzzed
 from wide_cases import canon, oracle_state
 
 B, CAP, STEPS = 37, 5, 9
@@ -42,11 +45,14 @@ class Recording:
     recorded step: canonical and packed states before the step and after the un-reset step, actions,
     rewards, dones.  run(k) records up to step k."""
 
-    def __init__(self, make, variant, na, train, capacity=CAP):
+    def __init__(self, make, variant, na, train, capacity=CAP, place=None, actions=None):
+        """`place(env)` puts the fresh env into its first state (default place_near_end); `actions(env,
+        s)` gives step s's actions [B, NA] (default the greedy 0.3 policy of the env's state)."""
         import warehouse
 
         self.env = make(variant, B, na, train=train, seed=SEED)
-        place_near_end(self.env)
+        (place or place_near_end)(self.env)
+        self.actions = actions or (lambda env, s: env.policy("greedy", 0.3).clone())
         self.buf = warehouse.ReplayBuffer(self.env, capacity)
         self.L = oc.layout_for(variant)
         self.T = self.env.geometry["T"]
@@ -57,7 +63,7 @@ class Recording:
         env, buf = self.env, self.buf
         while len(self.steps) < upto:
             s = len(self.steps)
-            acts = env.policy("greedy", 0.3).clone()
+            acts = self.actions(env, s)
             pre, pre_packed = canon(env), env.state.cpu().numpy().copy()
             slot = buf.cursor
             buf.put_obs(slot, acts)
@@ -174,6 +180,88 @@ def case_round_trip(make, variant, na, train):
         assert len({int(n) for s in rec.steps for n in s["pre"]["n"]}) > 1   # variable agent counts
 
 
+# ----------------------------------------------------------------------------- 1b. round trip, fuzzed
+# place_fuzzed seeds per VARIANTS id, (full, sparse), chosen on the host engine so that the floors of
+# case_round_trip_fuzzed hold at B = 37
+FUZZ_SEEDS = {"small4": (101, 122), "medium8": (103, 104), "medium1": (105, 106), "medium3": (107, 108),
+              "medium_train": (109, 110), "large16": (111, 112)}
+
+
+def uniform_actions(seed):
+    """actions(env, s) for Recording: seeded uniform integers in 0 .. 8 (no walk over the request
+    table, so a sparse table is allowed)."""
+    rng = np.random.default_rng(seed)
+
+    def actions(env, s):
+        a = rng.integers(0, 9, (env.B, env.agent_slots)).astype(np.int32)
+        return torch.as_tensor(a).to(env.device)
+
+    return actions
+
+
+def fuzzed_recording(make, variant, na, train, full):
+    seed = FUZZ_SEEDS[IDS[VARIANTS.index((variant, na, train))]][0 if full else 1]
+    return Recording(make, variant, na, train, place=lambda env: place_fuzzed(env, full, seed),
+                     actions=None if full else uniform_actions(seed))
+
+
+def fuzz_coverage(rec):
+    """What the recorded `pre` states of a Recording hold that place_near_end never reaches."""
+    R = rec.L.R
+    opened = [s["pre"]["pickup_target"] >= 0 for s in rec.steps]
+    ring = sorted(rec.slot_step.values())
+    return dict(
+        expiring=sum(int((o & (s["pre"]["pickup_timer"] == 1)).sum()) for o, s in zip(opened, rec.steps)),
+        expiring_below_w=sum(int((o & (s["pre"]["pickup_timer"] == 1) & (s["pre"]["t"] < rec.L.W - 1)[:, None]).sum())
+                             for o, s in zip(opened, rec.steps)),
+        steps_left=len(np.unique(np.concatenate([rec.steps[k]["pre"]["pickup_timer"][opened[k]] for k in ring]))),
+        dones=sum(int(s["dones"].sum()) for s in rec.steps),
+        rewards=sum(int((s["rewards"] != 0).sum()) for s in rec.steps),
+        sparse=sum(int((o.sum(1) < R).sum()) for o in opened),
+        after_done=sum(int(s["pre"]["episode"].astype(np.int64).clip(0, 1).sum()) for s in rec.steps))
+
+
+def case_round_trip_fuzzed(make, variant, na, train, full):
+    """case_round_trip's comparison from fuzz_states.place_fuzzed: after 4 and after 9 steps, a
+    permutation of every entry and a batch with repeats equal the oracle's rows of the captured states,
+    and the packed copies unpack to them.  full=False: sparse request tables and uniform actions.
+    The coverage the parent's cases lack is asserted on the recorded pre-step states (floors well
+    under what the host engine gives at B = 37): requests at timer 1 before a recorded step, distinct
+    steps-left values in the final ring, dones, rewards, and with full=False states below R requests."""
+    rec = fuzzed_recording(make, variant, na, train, full)
+    rng = np.random.default_rng(13)
+    for upto in (4, STEPS):
+        rec.run(upto)
+        N = len(rec.buf)
+        assert N == min(upto, CAP) * B
+        dup = rng.integers(0, N, 185)
+        dup[1::9] = dup[0]
+        for idx in (rng.permutation(N), dup):
+            got, want = gather(rec.buf, idx), rec.expected(idx)
+            assert set(got) == set(ALL_KEYS)
+            assert_batch(got, {k: want[k] for k in got}, f"{variant}/{na} full={full} after {upto} steps, M={len(idx)}: ")
+        idx = rng.permutation(N)[:B]
+        got, want = gather(rec.buf, idx, ("state", "next_state")), rec.expected(idx)
+        for key, side in (("state", "pre"), ("next_state", "post")):
+            twin = make(variant, B, na, train=train, seed=SEED)
+            twin.state.copy_(torch.as_tensor(got[key]).to(twin.device))
+            c = canon(twin)
+            for f, v in c.items():
+                ref = np.stack([rec.steps[k][side][f][j] for k, j in zip(want["step"], want["env"])])
+                np.testing.assert_array_equal(v, ref, err_msg=f"{key}.{f}")
+    assert len(rec.slot_step) == CAP and min(rec.slot_step.values()) == STEPS - CAP   # the ring wrapped
+    cov = fuzz_coverage(rec)
+    print(f"coverage {variant}/{na} train={train} full={full}: {cov}")
+    assert cov["expiring"] >= 20 and cov["expiring_below_w"] >= 1, cov
+    assert cov["steps_left"] >= 60, cov
+    assert cov["dones"] >= 10 and cov["rewards"] >= 1 and cov["after_done"] >= 1, cov
+    if full:
+        assert cov["sparse"] == 0, cov
+    else:
+        assert cov["sparse"] >= 1, cov
+    return cov
+
+
 # ----------------------------------------------------------------------------- 2. trajectory
 def case_step_keeps_trajectory(make, variant, na, train):
     """ReplayBuffer.step is vector_step(autoreset=True): two envs with one seed, one stepped through
@@ -266,27 +354,38 @@ def case_invalid_indices(make, variant, na, train):
 
 
 # ----------------------------------------------------------------------------- 5. fragments (device)
-def case_fragments(make, variant, na):
+def case_fragments(make, variant, na, rec=None, rows=False):
     """xfrag / next_xfrag are byte-equal to wh_observe_x on the gathered state / next_state planes as
-    a batch of M envs: M with whole 32-row tiles, and M with a tail tile."""
-    rec = Recording(make, variant, na, False).run(STEPS)
+    a batch of M envs: M with whole 32-row tiles, and M with a tail tile.  `rec`: a finished Recording
+    to gather from (default: one from place_near_end).  `rows`: also the gathered obs / next_obs
+    against wh_observe on the same planes."""
+    rec = rec or Recording(make, variant, na, False).run(STEPS)
     N = len(rec.buf)
     rng = np.random.default_rng(5)
     for M in (64, 37, 1):
         idx = rng.integers(0, N, M)
         idx[M // 2] = -1                                       # an invalid sample among them
-        keys = ("xfrag", "next_xfrag", "state", "next_state", "n")
+        keys = ("xfrag", "next_xfrag", "state", "next_state", "n") + (("obs", "next_obs") if rows else ())
         raw, out = guarded(rec.buf, M, keys)
         got = rec.buf.sample(M, idx=idx, out=out)
         assert_guards(raw)
         assert got["n"][M // 2].item() == -1
         assert (M * na) % 32 == 0 or M != 64
         twin = make(variant, M, na, seed=SEED)
-        for fk, sk in (("xfrag", "state"), ("next_xfrag", "next_state")):
+        for fk, sk, ok in (("xfrag", "state", "obs"), ("next_xfrag", "next_state", "next_obs")):
             twin.state.copy_(got[sk])
             ref = twin.observe_x()
             assert ref.shape == got[fk].shape
             assert torch.equal(ref, got[fk]), f"{fk} differs (M = {M})"
+            if rows:
+                assert torch.equal(twin.observe(), got[ok]), f"{ok} differs from wh_observe of {sk} (M = {M})"
+
+
+def case_fragments_fuzzed(make, variant, na):
+    """case_fragments on a fuzzed recording (small steps-left values, crowded agents, clocks from 0 to
+    T; full and sparse request tables), with the gathered rows against wh_observe of the gathered planes."""
+    for full in (True, False):
+        case_fragments(make, variant, na, rec=fuzzed_recording(make, variant, na, False, full).run(STEPS), rows=True)
 
 
 # ----------------------------------------------------------------------------- 6. portability (device)

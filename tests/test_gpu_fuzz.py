@@ -10,6 +10,8 @@ import pytest
 from oracle import batched as ob
 from oracle import core as oc
 
+from fuzz_states import random_states
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,42 +23,6 @@ def wh():
     import warehouse
 
     return warehouse
-
-
-def random_states(L, B, nmax, rng, ts=None, full=False):
-    P, Dp, R, W, D = L.P, L.Dp, L.R, L.W, L.D
-    pk, dl, _, _ = ob.tables(L)
-    n = rng.randint(1, nmax + 1, size=B)
-    pos = np.zeros((B, nmax, 2), np.int32)
-    atg = np.full((B, nmax), -1, np.int32)
-    tgt = np.full((B, P), -1, np.int32)
-    tim = np.full((B, P), -1, np.int32)
-    t = rng.choice(ts if ts is not None else [0, 5, L.T - 1, L.T, 150], size=B).astype(np.int64)
-    for e in range(B):
-        k = n[e]
-        mode = rng.randint(4)
-        if mode == 0:
-            cx, cy = rng.randint(0, D - 2, size=2)
-            p = np.stack([cx + rng.randint(0, 3, k), cy + rng.randint(0, 3, k)], 1)
-        elif mode == 1:
-            c = pk[rng.randint(P)]
-            p = np.stack([c[0] + rng.randint(-1, 2, k), c[1] + rng.randint(-1, 2, k)], 1)
-        elif mode == 2:
-            c = dl[rng.randint(Dp)]
-            p = np.stack([c[0] + rng.randint(-1, 2, k), c[1] + rng.randint(-1, 2, k)], 1)
-        else:
-            p = rng.randint(0, D, size=(k, 2))
-        pos[e, :k] = np.clip(p, 0, D - 1)
-        na = R if full else rng.randint(max(0, R - k), R + 1)
-        sel = rng.choice(P, na, replace=False)
-        tgt[e, sel] = rng.randint(0, Dp, na)
-        tim[e, sel] = np.where(rng.rand(na) < 0.3, 1, rng.randint(1, W + 1, na))
-        a = np.where(rng.rand(k) < 0.4, rng.randint(0, Dp, k), -1)
-        for i in range(k):
-            if a[i] >= 0 and rng.rand() < 0.5:
-                pos[e, i] = np.clip(dl[a[i]] + rng.randint(-1, 2, 2), 0, D - 1)
-        atg[e, :k] = a
-    return n.astype(np.int32), pos, atg, tgt, tim, t
 
 
 def run_fuzz(wh, variant, ordered, seed, ts=None, B=3000):

@@ -35,6 +35,12 @@ def test_round_trip_against_the_oracle(make, variant, na, train):
     rc.case_round_trip(make, variant, na, train)
 
 
+@pytest.mark.parametrize("full", [True, False], ids=["full", "sparse"])
+@pytest.mark.parametrize("variant,na,train", rc.VARIANTS, ids=rc.IDS)
+def test_round_trip_from_fuzzed_states(make, variant, na, train, full):
+    rc.case_round_trip_fuzzed(make, variant, na, train, full)
+
+
 @pytest.mark.parametrize("variant,na,train", [("medium", 8, False), ("medium", None, True)], ids=["medium8", "medium_train"])
 def test_step_leaves_the_trajectory_alone(make, variant, na, train):
     rc.case_step_keeps_trajectory(make, variant, na, train)
@@ -60,6 +66,11 @@ def test_invalid_indices(make, variant, na, train):
                          ids=["medium8", "medium1", "medium9", "large16"])
 def test_fragments(make, variant, na):
     rc.case_fragments(make, variant, na)
+
+
+@pytest.mark.parametrize("variant,na", [("medium", 8), ("medium", 1), ("large", 16)], ids=["medium8", "medium1", "large16"])
+def test_fragments_and_rows_from_fuzzed_states(make, variant, na):
+    rc.case_fragments_fuzzed(make, variant, na)
 
 
 @pytest.mark.parametrize("variant,na,train", [("medium", 8, False), ("medium", None, True)], ids=["medium8", "medium_train"])

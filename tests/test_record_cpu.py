@@ -36,6 +36,34 @@ def test_ring_equal_with_37_envs():
     rec.case_ring_equal(make, "medium", 8, False, nb=rc.B)
 
 
+@pytest.mark.parametrize("variant,na,train", rc.VARIANTS, ids=rc.IDS)
+def test_ring_equal_from_fuzzed_states(variant, na, train):
+    rec.case_ring_equal_fuzzed(make, variant, na, train, True)
+
+
+@pytest.mark.parametrize("variant,na,train", [("medium", 8, False), ("medium", None, True), ("large", 16, False)],
+                         ids=["medium8", "medium_train", "large16"])
+def test_ring_equal_from_sparse_fuzzed_states(variant, na, train):
+    rec.case_ring_equal_fuzzed(make, variant, na, train, False)
+
+
+@pytest.mark.parametrize("policy,p", [("greedy", 0.3), ("greedy", 0.0), ("random", 0.0)],
+                         ids=["greedy03", "greedy0", "random"])
+@pytest.mark.parametrize("variant,na,train",
+                         [("small", 4, False), ("medium", 8, False), ("medium", None, True), ("large", 16, False)],
+                         ids=["small4", "medium8", "medium_train", "large16"])
+def test_collect_from_fuzzed_states_against_the_oracle(variant, na, train, policy, p):
+    rec.case_collect_fuzzed(make, variant, na, train, policy, p)
+
+
+def test_collect_from_fuzzed_states_into_a_prioritized_buffer():
+    rec.case_collect_fuzzed(make, "medium", 8, False, "greedy", 0.3, prioritized=True)
+
+
+def test_collect_steps_on_after_its_own_resets():
+    rec.case_collect_steps_on_after_resets(make)
+
+
 @pytest.mark.parametrize("policy,p", [("greedy", 0.3), ("random", 0.0)], ids=["greedy", "random"])
 @pytest.mark.parametrize("variant,na,train", [("medium", 8, False), ("medium", None, True), ("small", 4, False)],
                          ids=["medium8", "medium_train", "small4"])

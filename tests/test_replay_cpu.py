@@ -33,6 +33,12 @@ def test_round_trip_against_the_oracle(variant, na, train):
     rc.case_round_trip(make, variant, na, train)
 
 
+@pytest.mark.parametrize("full", [True, False], ids=["full", "sparse"])
+@pytest.mark.parametrize("variant,na,train", rc.VARIANTS, ids=rc.IDS)
+def test_round_trip_from_fuzzed_states(variant, na, train, full):
+    rc.case_round_trip_fuzzed(make, variant, na, train, full)
+
+
 @pytest.mark.parametrize("variant,na,train", [("medium", 8, False), ("medium", None, True)], ids=["medium8", "medium_train"])
 def test_step_leaves_the_trajectory_alone(variant, na, train):
     rc.case_step_keeps_trajectory(make, variant, na, train)

@@ -156,7 +156,7 @@ def case_fuzz(make, variant, B=1237, seed=41):
     """One philox-regenerated step from adversarial states (crowded, overlapping agents, timers about
     to expire, t in {0, 5, 150, T-1, T}); B is odd: a partial last group, wave and workgroup; Train
     slots, so n < slots leaves idle lanes."""
-    from test_gpu_fuzz import random_states
+    from fuzz_states import random_states
 
     L = oc.layout_for(variant)
     nmax = oc.VARIANTS[variant]["nmax"]
