@@ -1,5 +1,5 @@
 // The host engine's replay priority tree (csrc/host_engine.cpp: wh_replay_prio_*) under
-// AddressSanitizer + UndefinedBehaviorSanitizer: trees of 1 .. 4 levels with buffers of exactly the
+// AddressSanitizer + UndefinedBehaviorSanitizer: trees of 1 .. 6 levels (up to 1,048,577 leaves) with buffers of exactly the
 // sizes wh_replay_prio_query states, fills over every kind of range, updates with duplicate and
 // invalid indices and the quantisation's edge values, samples from injected and philox draws, the
 // largest sums, the empty tree and the refusals -- so any read or write past a buffer, any signed
@@ -136,7 +136,8 @@ void exercise(int64_t count, uint64_t seed) {
 }  // namespace
 
 int main() {
-  for (int64_t count : {(int64_t)1, (int64_t)16, (int64_t)17, (int64_t)333, (int64_t)4099}) exercise(count, 40 + (uint64_t)count);
+  for (int64_t count : {(int64_t)1, (int64_t)16, (int64_t)17, (int64_t)333, (int64_t)4099, (int64_t)65537, (int64_t)1048577})
+    exercise(count, 40 + (uint64_t)count);
   int64_t lw = 0, nw = 0;
   int32_t lv = 0;
   EXPECT(wh_replay_prio_query(0, &lw, &nw, &lv) == WH_EINVAL);

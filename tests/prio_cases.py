@@ -6,6 +6,11 @@ buffer-level bodies take an env factory like tests/replay_cases.py.  The numpy m
 here: quantisation, level sums recomputed from the leaves, the inverse CDF as np.cumsum on uint64 +
 searchsorted, the philox masses from oracle/philox.py with Python integers for the 64 x 64 high
 product.  Every comparison is at tolerance 0 except the importance weights.
+
+The small counts (COUNTS, one to four levels) take the full sequences; so do DEEP_COUNTS (five and
+six levels, the sizes a real buffer has).  Seven levels take a reduced sequence with few whole-tree
+copies, eight levels a tree that is almost all zeros against SparseModel; case_launch_widths and
+case_unaligned_fills are the launches of thousands of workgroups.
 """
 import ctypes
 
@@ -16,7 +21,21 @@ from oracle import philox as oph
 
 ONE, QMAX = 1 << 20, 0x7FFFFFFF
 COUNTS = (1, 16, 17, 333, 4099)          # 1, 1, 2, 3, 4 levels above the leaves
-LEVELS = dict(zip(COUNTS, (1, 1, 2, 3, 4)))
+# 65,537: five levels, the last leaf alone in its entry at every level; 2^20: five levels and no
+# padding anywhere; 2^20 + 1: six levels
+DEEP_COUNTS = (65537, 1 << 20, (1 << 20) + 1)
+COUNT_7, COUNT_8 = (1 << 24) + 1, (1 << 28) + 1   # seven levels (reduced body), eight (sparse body)
+
+
+def levels_of(count):
+    """Levels above the leaves: the smallest K >= 1 with 16^K >= count."""
+    k = 1
+    while 16 ** k < count:
+        k += 1
+    return k
+
+
+LEVELS = {c: levels_of(c) for c in COUNTS + DEEP_COUNTS + (COUNT_7, COUNT_8)}
 GUARD = 256
 SEED = 0x5EED0000BEEF
 MASK64 = (1 << 64) - 1
@@ -93,6 +112,61 @@ class Model:
         return idx, self.leaf[idx]
 
 
+class SparseModel:
+    """Model for trees too large for a dense host copy: the non-zero leaves as a sorted index array
+    and their values.  tests/test_prio_cpu.py holds it equal to Model on the same operations."""
+
+    def __init__(self, count):
+        self.count = count
+        self.idx = np.zeros(0, np.int64)
+        self.val = np.zeros(0, np.uint32)
+        self.max_q = ONE
+
+    def _replace(self, idx, val):
+        """Leaves `idx` (unique) take `val`; a zero value removes the leaf."""
+        keep = ~np.isin(self.idx, idx)
+        idx, val = idx[val > 0], val[val > 0]
+        ai, av = np.concatenate([self.idx[keep], idx]), np.concatenate([self.val[keep], val])
+        order = np.argsort(ai, kind="stable")
+        self.idx, self.val = ai[order], av[order].astype(np.uint32)
+
+    def fill(self, first, n, mode, q=0):
+        self._replace(np.arange(first, first + n, dtype=np.int64), np.full(n, self.max_q if mode else q, np.uint32))
+
+    def update(self, idx, p):
+        idx, q = np.asarray(idx, np.int64), quantise(p)
+        ok = (idx >= 0) & (idx < self.count)
+        idx, q = idx[ok], q[ok]
+        if not len(q):
+            return
+        order = np.lexsort((q, idx))                                  # by leaf, then by q: a leaf's last is its largest
+        idx, q = idx[order], q[order]
+        last = np.append(idx[1:] != idx[:-1], True)
+        self._replace(idx[last], q[last])
+        self.max_q = max(self.max_q, int(q.max()))
+
+    def level(self, k):
+        """(indices, values as uint64) of the non-zero entries of level k (0: the leaves)."""
+        if k == 0:
+            return self.idx, self.val.astype(np.uint64)
+        u, inv = np.unique(self.idx >> (4 * k), return_inverse=True)
+        s = np.zeros(len(u), np.uint64)
+        np.add.at(s, inv, self.val.astype(np.uint64))
+        return u, s
+
+    def total(self):
+        return int(self.val.astype(np.uint64).sum(dtype=np.uint64))
+
+    def sample(self, r):
+        total = self.total()
+        if total == 0:
+            return np.full(len(r), -1, np.int64), np.zeros(len(r), np.uint32)
+        c = np.cumsum(self.val.astype(np.uint64), dtype=np.uint64)
+        mass = np.array([(int(x) * total) >> 64 for x in r], np.uint64)
+        at = np.searchsorted(c, mass, side="right")
+        return self.idx[at], self.val[at]
+
+
 def philox_draws(seed, draw, M):
     m = np.arange(M, dtype=np.uint64)
     c = oph.philox4x32_10(m, draw & 0xFFFFFFFF, draw >> 32, 7 << 24, seed & 0xFFFFFFFF, seed >> 32)
@@ -108,8 +182,10 @@ def draw_for_mass(mass, total):
 
 # ----------------------------------------------------------------------------- a tree behind the C ABI
 def _guarded(nbytes, device, fill=0):
-    raw = torch.full((nbytes + GUARD,), 0xA5, dtype=torch.uint8, device=device)
-    raw[:nbytes] = fill
+    # (zeros, not a fill: an eight-level tree's 1.1 GB of leaves are never touched on the host)
+    raw = torch.full((nbytes + GUARD,), fill, dtype=torch.uint8, device=device) if fill else \
+        torch.zeros(nbytes + GUARD, dtype=torch.uint8, device=device)
+    raw[nbytes:] = 0xA5
     return raw
 
 
@@ -179,6 +255,44 @@ class Tree:
         np.testing.assert_array_equal(node, want_node, err_msg=f"{what}: sums")
         assert not leaf[self.count:].any() and int(node[shape(self.count)[2][-1][1]]) == model.total(), what
         assert max_q == model.max_q, f"{what}: max_q {max_q}, expected {model.max_q}"
+
+    def leaf_at(self, idx):
+        """leaf[idx] as numpy uint32, indexed on the buffer's own device (no whole-tree copy)."""
+        leaf = self.raw["leaf"][:self.sizes["leaf"]].view(torch.int32)
+        return leaf[torch.as_tensor(np.asarray(idx, np.int64)).to(self.device)].cpu().numpy().view(np.uint32)
+
+    def check_sparse(self, model, what=""):
+        """check() against a SparseModel without a dense host copy: per level, the non-zero entries
+        of the level's whole slice (padding included) by torch.nonzero on the buffer's device, their
+        indices and values the model's; the guards and max_q read on their own."""
+        lw, nw, levels = shape(self.count)
+        leaf = self.raw["leaf"][:self.sizes["leaf"]].view(torch.int32)
+        node = self.raw["node"][:self.sizes["node"]].view(torch.int64)
+        assert len(levels) == LEVELS[self.count]
+        for k in range(len(levels) + 1):
+            if k == 0:
+                part = leaf
+            else:
+                n, off = levels[k - 1]
+                part = node[off:off + (n + 15) // 16 * 16]
+            at = torch.nonzero(part).flatten()
+            got_idx, got_val = at.cpu().numpy(), part[at].cpu().numpy()
+            got_val = got_val.view(np.uint32).astype(np.uint64) if k == 0 else got_val.view(np.uint64)
+            want_idx, want_val = model.level(k)
+            np.testing.assert_array_equal(got_idx, want_idx, err_msg=f"{what}: level {k}, non-zero entries")
+            np.testing.assert_array_equal(got_val, want_val, err_msg=f"{what}: level {k}, values")
+        root = levels[-1][1]
+        assert int(node[root].item()) == model.total(), what
+        for k, v in self.raw.items():
+            assert bool((v[self.sizes[k]:] == 0xA5).all()), f"bytes written past the end of {k}"
+        max_q = int(self.raw["max_q"][:4].cpu().numpy().view(np.uint32)[0])
+        assert max_q == model.max_q, f"{what}: max_q {max_q}, expected {model.max_q}"
+
+    def free(self):
+        """Drop the buffers (and hand a device's cached blocks back) before the next test."""
+        self.raw = {}
+        if str(self.device) != "cpu":
+            torch.cuda.empty_cache()
 
 
 QUANT_TABLE = np.array([np.nan, 0.0, -0.0, -3.5, 1e-9, 2.0 ** -20, 1.0, 2047.9, 2048.0, 1e30, np.inf], np.float32)
@@ -269,7 +383,8 @@ def assert_samples(t, m, M, u=None, draw=0, what=""):
     np.testing.assert_array_equal(q, want_q, err_msg=f"{what} M={M}: q")
     assert total == m.total(), what
     if total:
-        np.testing.assert_array_equal(q, t.read()[0][idx])            # q_out == leaf[idx_out]
+        # q_out == leaf[idx_out] (from seven levels up read at idx alone, not through a whole-tree copy)
+        np.testing.assert_array_equal(q, t.read()[0][idx] if t.count <= DEEP_COUNTS[-1] else t.leaf_at(idx))
         assert (q > 0).all()
     return idx
 
@@ -341,8 +456,181 @@ def case_portability(nat, count):
         np.testing.assert_array_equal(a[0], md.sample(philox_draws(SEED, draw, M))[0])
 
 
-# ----------------------------------------------------------------------------- 4. the buffer
+# ----------------------------------------------------------------------------- 4. seven and eight levels
+def case_seven_levels(nat, lib, device):
+    """16,777,217 leaves, seven levels: a reduced sequence (the full one would copy 73 MB back per
+    operation), the whole tree compared with the model after each of its six steps."""
+    count = COUNT_7
+    assert len(shape(count)[2]) == LEVELS[count] == 7
+    t, m = Tree(nat, lib, device, count), Model(count)
+    rng = np.random.default_rng(7)
+    try:
+        def both(what, op, *args):
+            getattr(t, op)(*args)
+            getattr(m, op)(*args)
+            t.check(m, f"seven levels: {what}")
+
+        both("whole-tree fill", "fill", 0, count, 0, ONE)
+        # off a workgroup's 256, over a level-5 entry boundary (a multiple of 2^20), 587 workgroups
+        first, n = 5 * (1 << 20) - 70001, 150000
+        assert first % 256 and (first >> 20) + 1 == (first + n - 1) >> 20
+        both("unaligned fill", "fill", first, n, 0, int(rng.integers(1, QMAX)))
+        M = 5000
+        idx, p = rng.integers(0, count, M), rng.uniform(0.0, 40.0, M).astype(np.float32)
+        idx[1], idx[M - 1] = idx[2], idx[0]                           # duplicates within and across workgroups
+        idx[5], idx[6] = count - 1, first + 3
+        idx[10], idx[300], idx[4000] = -1, count, 1 << 40             # ignored
+        both("update", "update", idx, p)
+        # philox and injected draws, the ends, and the prefix boundaries on both sides of that fill
+        assert_samples(t, m, 4096, draw=(7 << 32) | 1, what="seven levels philox")
+        u = [int(x) for x in rng.integers(0, 1 << 64, 1000, dtype=np.uint64)]
+        assert_samples(t, m, len(u), u=u, what="seven levels injected")
+        ends = assert_samples(t, m, 2, u=[0, MASK64], what="seven levels ends")
+        assert list(ends) == [0, count - 1]
+        c, total = np.cumsum(m.leaf.astype(np.uint64), dtype=np.uint64), m.total()
+        assert m.leaf.all()
+        u = [draw_for_mass(int(c[i]) - d, total) for i in (first - 1, first + n - 1) for d in (1, 0)]
+        got = assert_samples(t, m, 4, u=u, what="seven levels boundaries")
+        assert list(got) == [first - 1, first, first + n - 1, first + n]
+        t.check(m, "seven levels: after the samples")
+        both("all max", "fill", 0, count, 0, QMAX)
+        assert m.total() == count * QMAX and m.total() > 1 << 54
+        got = assert_samples(t, m, 1000, draw=11, what="seven levels all max")
+        assert len(np.unique(got >> 20)) >= 16                        # under every full level-5 entry
+        ends = assert_samples(t, m, 2, u=[0, MASK64], what="seven levels all max, ends")
+        assert list(ends) == [0, count - 1]
+        both("empty", "fill", 0, count, 0, 0)
+        assert m.total() == 0
+        for kw in (dict(draw=1), dict(u=[0, 5, MASK64])):
+            idx, q, total = t.sample(3, **kw)
+            assert (idx == -1).all() and not q.any() and total == 0
+    finally:
+        t.free()
+
+
+def case_eight_levels_sparse(nat, lib, device):
+    """2^28 + 1 leaves, eight levels (1.1 GB of leaves, all but some 70,000 zero) against SparseModel,
+    every level checked by its non-zero entries on the buffer's own device.  The root of this tree
+    has two children (leaves 0 .. 2^28 - 1 and the last leaf alone); level 6, with 17 entries of
+    2^24 leaves each, is the highest level with more than two, so the spread of the philox sample
+    is asserted over three of those."""
+    count = COUNT_8
+    assert len(shape(count)[2]) == LEVELS[count] == 8 and shape(count)[2][-2][0] == 2
+    t, m = Tree(nat, lib, device, count), SparseModel(count)
+    rng = np.random.default_rng(8)
+    try:
+        def both(what, op, *args):
+            getattr(t, op)(*args)
+            getattr(m, op)(*args)
+            t.check_sparse(m, f"eight levels: {what}")
+
+        t.check_sparse(m, "eight levels: empty")
+        idx = rng.integers(1 << 20, count - (1 << 20), 300)
+        both("random update", "update", idx, rng.uniform(1e-3, 30.0, 300).astype(np.float32))
+        ends = assert_samples(t, m, 2, u=[0, MASK64], what="eight levels ends")
+        assert list(ends) == [idx.min(), idx.max()]                   # the first and last non-zero leaf
+        edge = np.array([0, 15, 16, (1 << 24) - 1, 1 << 24, (1 << 28) - 1, 1 << 28, -1, (1 << 31) + 5, 777777, 777777])
+        p = rng.uniform(1e-3, 30.0, len(edge)).astype(np.float32)
+        both("update at the edges", "update", edge, p)
+        valid = edge[(edge >= 0) & (edge < count)]
+        assert (t.leaf_at(valid) > 0).all() and t.leaf_at([777777])[0] == quantise(p[-2:]).max()
+        # from an unaligned start over a level-6 entry boundary (a multiple of 2^24)
+        first, n = 3 * (1 << 24) - 33001, 70000
+        assert first % 256 and (first >> 24) + 1 == (first + n - 1) >> 24
+        both("fill over a level-6 boundary", "fill", first, n, 0, int(rng.integers(1, ONE)))
+        # the last 300 leaves at a q that gives them 1/17 of the total: about 240 of 4,096 rows
+        q = m.total() // (16 * 300)
+        assert 5 < q <= QMAX
+        both("fill of the last 300", "fill", count - 300, 300, 0, q)
+        got = assert_samples(t, m, 4096, draw=(8 << 32) | 3, what="eight levels philox")
+        assert (got >= count - 300).sum() >= 10, "the philox sample misses the last 300 leaves"
+        assert len(np.unique(got >> 24)) >= 3, "the philox sample stays under two level-6 entries"
+        u = [int(x) for x in rng.integers(0, 1 << 64, 1000, dtype=np.uint64)]
+        assert_samples(t, m, len(u), u=u, what="eight levels injected")
+        ends = assert_samples(t, m, 2, u=[0, MASK64], what="eight levels ends")
+        assert list(ends) == [0, count - 1] and (m.idx[0], m.idx[-1]) == (0, count - 1)
+    finally:
+        t.free()
+
+
+# ----------------------------------------------------------------------------- 5. launch widths
+def case_launch_widths(nat, lib, device, count):
+    """One update of 2^20 samples (4,096 workgroups, every leaf a duplicate across many of them), a
+    second one on top that lowers every leaf, and samples of 65,541 rows (a ragged last workgroup).
+    Returns the final (leaf, node, max_q) for the comparison between the engines."""
+    t, m = Tree(nat, lib, device, count), Model(count)
+    rng = np.random.default_rng(4000 + count)
+    M = 1 << 20
+    for tt in (t, m):
+        tt.fill(0, count, 0, ONE)
+    nodes, top = [], ONE
+    for lo, hi in ((1.0, 40.0), (0.0, 0.5)):
+        idx, p = rng.integers(-3, count + 3, M), rng.uniform(lo, hi, M).astype(np.float32)
+        ok = (idx >= 0) & (idx < count)
+        assert (~ok).sum() >= 1
+        per_leaf = np.bincount(idx[ok], minlength=count)
+        assert per_leaf.min() >= (100 if count == 4099 else 1), per_leaf.min()
+        for tt in (t, m):
+            tt.update(idx, p)
+        t.check(m, f"count {count}: update of 2^20 samples in [{lo}, {hi})")
+        # the per-leaf maximum, worked out by sorting (not the model's np.maximum.at)
+        q = quantise(p)
+        order = np.lexsort((q[ok], idx[ok]))
+        si, sq = idx[ok][order], q[ok][order]
+        last = np.append(si[1:] != si[:-1], True)
+        want = np.zeros(count, np.uint32)
+        want[si[last]] = sq[last]
+        leaf, node, max_q = t.read()
+        np.testing.assert_array_equal(leaf[:count], want)
+        top = max(top, int(q[ok].max()))
+        assert max_q == top
+        nodes.append(node.copy())                                     # (on the host engine read() is a view)
+    # the second update's clear phase took mass out of every ancestor
+    assert (nodes[1][nodes[0] > 0] < nodes[0][nodes[0] > 0]).all() and (nodes[0] > 0).sum() == sum(n for n, _ in shape(count)[2])
+    Ms = 65541
+    assert_samples(t, m, Ms, draw=(4 << 32) | 9, what=f"count {count} philox")
+    u = [int(x) for x in rng.integers(0, 1 << 64, Ms, dtype=np.uint64)]
+    assert_samples(t, m, Ms, u=u, what=f"count {count} injected")
+    return t.read()
+
+
+FILL_SHAPES = ((1, 65536), (255, 258), (257, 4095), (4095, 61442), (65521, 16), (65536, 1), (-300, 300))
+
+
+def case_unaligned_fills(nat, lib, device, count):
+    """Fills that start off a workgroup's 256 leaves and run over many workgroups, each with a fresh
+    q, then the same shapes in mode 1 after an update has raised max_q.  (first < 0: from the end.)
+    Returns the final (leaf, node, max_q)."""
+    t, m = Tree(nat, lib, device, count), Model(count)
+    rng = np.random.default_rng(5000 + count)
+    idx, p = rng.integers(0, count, 5000), rng.uniform(0.0, 8.0, 5000).astype(np.float32)
+    for tt in (t, m):
+        tt.update(idx, p)
+    t.check(m, "scattered start")
+    for mode in (0, 1):
+        for j, (first, n) in enumerate(FILL_SHAPES):
+            first = first % count
+            assert first + n <= count
+            if mode:                                                  # a new max_q: every fill writes new values
+                for tt in (t, m):
+                    tt.update([count // 2], [1500.0 + j])
+            q = int(rng.integers(0, QMAX + 1))                         # drawn once, given to both
+            for tt in (t, m):
+                tt.fill(first, n, mode, q)
+            t.check(m, f"count {count}: fill({first}, {n}, mode {mode})")
+            assert (t.read()[0][first:first + n] == (m.max_q if mode else q)).all()
+        if mode == 0:
+            for tt in (t, m):
+                tt.update([count // 2, 3], [1500.0, 0.25])
+            t.check(m, "max_q raised")
+            assert m.max_q == 1500 << 20
+    assert m.max_q == 1506 << 20
+    return t.read()
+
+
+# ----------------------------------------------------------------------------- 6. the buffer
 B, CAP, STEPS = 37, 9, 12                                             # 333 leaves: three levels
+BIG = dict(B=8200, cap=9, levels=5, leaf_words=73808, n_update=70000, big_M=4096)   # 73,800 leaves: five levels
 
 
 def buffer_tree(buf):
@@ -359,21 +647,53 @@ def assert_buffer_tree(buf, m, what):
     assert max_q == m.max_q, what
 
 
-def case_buffer(make, variant, na):
-    """A prioritized ReplayBuffer over 12 recorded steps of a capacity-9 ring: a recorded slot's
-    leaves are max_q, unrecorded slots are 0 and never drawn, update_priorities is the model's
+def expected_uniform_draw(seed, draw, M, filled, B):
+    """replay_cases.expected_draw (philox purpose 6) for a buffer of B envs (that one reads its own B)."""
+    m = np.arange(M, dtype=np.uint64)
+    c = oph.philox4x32_10(m, draw & 0xFFFFFFFF, draw >> 32, 6 << 24, seed & 0xFFFFFFFF, seed >> 32)
+    return oph.uniform_int(filled, c[0]) * B + oph.uniform_int(B, c[1])
+
+
+def case_buffer(make, variant, na, B=B, cap=CAP, levels=3, leaf_words=336, n_update=150, big_M=37):
+    """A prioritized ReplayBuffer over 12 recorded steps of a capacity-`cap` ring of B envs: a recorded
+    slot's leaves are max_q, unrecorded slots are 0 and never drawn, update_priorities is the model's
     update of (|p| + eps) ** alpha, sample(M) draws the model's indices, returns what the explicit
-    gather of them returns, and weights by the stated formula."""
+    gather of them returns, and weights by the stated formula; then one collect() whose steps wrap
+    the ring, so its slots' fill goes out in two parts.  (B = 8,200: five levels, every slot's fill
+    starts off a workgroup's 256 leaves and spans 33 workgroups.)"""
     import warehouse
     from replay_cases import place_near_end
 
     env = make(variant, B, na, seed=SEED)
     place_near_end(env)
-    buf = warehouse.ReplayBuffer(env, CAP, prioritized=True, alpha=0.6, eps=1e-6)
-    assert buf.prio_levels == 3 and buf.prio_leaf.numel() == 336 and buf.prio_leaf.device == env.state.device
-    m = Model(CAP * B)
+    buf = warehouse.ReplayBuffer(env, cap, prioritized=True, alpha=0.6, eps=1e-6)
+    assert buf.prio_levels == levels == LEVELS.get(cap * B, levels_of(cap * B))
+    assert buf.prio_leaf.numel() == leaf_words and buf.prio_leaf.device == env.state.device
+    m = Model(cap * B)
     rng = np.random.default_rng(17)
     assert_buffer_tree(buf, m, "fresh buffer")
+
+    def assert_sample(M, beta, draw, N):
+        got = {k: v.clone() for k, v in buf.sample(M, draw=draw, states=True, beta=beta).items()}
+        want_idx, want_q = m.sample(philox_draws(SEED, draw, M))
+        np.testing.assert_array_equal(got["idx_out"].cpu().numpy(), want_idx)
+        np.testing.assert_array_equal(got["prio_q"].cpu().numpy().view(np.uint32), want_q)
+        assert want_idx.max() < N and int(buf.prio_total.item()) == m.total()
+        again = buf.sample(M, idx=got["idx_out"], states=True)
+        assert set(got) == set(again) | {"prio_q", "weights"}
+        for k, v in again.items():
+            assert torch.equal(v, got[k]), f"{k} differs from the explicit gather"
+        w = (want_q.astype(np.float64) / np.float64(m.total()) * N) ** -beta
+        w = w / w.max()
+        assert got["weights"].dtype == torch.float32
+        np.testing.assert_allclose(got["weights"].cpu().numpy(), w, rtol=1e-6, atol=0)
+
+    def update(idx, td, what):
+        buf.update_priorities(idx, td)
+        p = ((torch.as_tensor(td).to(env.device).abs() + buf.eps) ** buf.alpha).cpu().numpy()
+        m.update(idx, p)
+        assert_buffer_tree(buf, m, what)
+
     for s in range(STEPS):
         slot = buf.cursor
         buf.step(env.policy("greedy", 0.3))
@@ -387,37 +707,36 @@ def case_buffer(make, variant, na):
             if s == 3:
                 got = buf.sample(1000, draw=77)["idx_out"].cpu().numpy()
                 assert got.max() < N and len(np.unique(got // B)) == 4   # never an unrecorded slot
-            idx = rng.integers(0, N, 150)
+            idx = rng.integers(0, N, n_update)
             idx[3] = idx[4]
-            td = rng.normal(0.0, 3.0, 150).astype(np.float32)
+            td = rng.normal(0.0, 3.0, n_update).astype(np.float32)
             td[:3] = (0.0, 4000.0, -2.5)                              # eps alone; raises max_q; a negative error
-            buf.update_priorities(idx, td)
-            p = ((torch.as_tensor(td).to(env.device).abs() + buf.eps) ** buf.alpha).cpu().numpy()
-            m.update(idx, p)
-            assert_buffer_tree(buf, m, f"update at step {s}")
+            update(idx, td, f"update at step {s}")
             assert m.max_q > ONE
-        for M, beta in ((64, 0.4), (37, 1.0)):
-            draw = (s << 8) | M
-            got = {k: v.clone() for k, v in buf.sample(M, draw=draw, states=True, beta=beta).items()}
-            want_idx, want_q = m.sample(philox_draws(SEED, draw, M))
-            np.testing.assert_array_equal(got["idx_out"].cpu().numpy(), want_idx)
-            np.testing.assert_array_equal(got["prio_q"].cpu().numpy().view(np.uint32), want_q)
-            assert want_idx.max() < N and int(buf.prio_total.item()) == m.total()
-            again = buf.sample(M, idx=got["idx_out"], states=True)
-            assert set(got) == set(again) | {"prio_q", "weights"}
-            for k, v in again.items():
-                assert torch.equal(v, got[k]), f"{k} differs from the explicit gather"
-            w = (want_q.astype(np.float64) / np.float64(m.total()) * N) ** -beta
-            w = w / w.max()
-            assert got["weights"].dtype == torch.float32
-            np.testing.assert_allclose(got["weights"].cpu().numpy(), w, rtol=1e-6, atol=0)
-    assert buf.filled == CAP and buf.cursor == STEPS % CAP
+        for M, beta in ((64, 0.4), (big_M, 1.0)):
+            assert_sample(M, beta, (s << 8) | M, N)
+    assert buf.filled == cap and buf.cursor == STEPS % cap
     # uniform=True and idx=... are the plain paths
     plain = buf.sample(16, draw=5, uniform=True)
     assert "weights" not in plain and "prio_q" not in plain
-    from replay_cases import expected_draw   # (its B is this file's: 37)
+    want = expected_uniform_draw(SEED, 5, 16, cap, B)
+    if B == 37:
+        from replay_cases import expected_draw   # (its B is this file's small one: 37)
 
-    np.testing.assert_array_equal(plain["idx_out"].cpu().numpy(), expected_draw(SEED, 5, 16, CAP))
+        np.testing.assert_array_equal(want, expected_draw(SEED, 5, 16, cap))
+    np.testing.assert_array_equal(plain["idx_out"].cpu().numpy(), want)
+    # every entry below max_q, then a collect() over the end of the ring: its slots enter at max_q
+    # through two fills, [cursor, cap) and [0, K - (cap - cursor))
+    N, K = len(buf), cap - 1
+    update(np.arange(N), rng.uniform(0.0, 2.0, N).astype(np.float32), "update of every entry")
+    cursor = buf.cursor
+    assert 0 < cap - cursor < K and (buffer_tree(buf)[0][:N] < m.max_q).all()
+    buf.collect(K, "greedy", 0.3, observe=False)
+    m.fill(cursor * B, (cap - cursor) * B, 1)
+    m.fill(0, (K - (cap - cursor)) * B, 1)
+    assert_buffer_tree(buf, m, "collect over the end of the ring")
+    assert buf.cursor == (cursor + K) % cap and (m.leaf == m.max_q).sum() == K * B
+    assert_sample(big_M, 0.4, 0x7000 | big_M, N)
 
 
 def case_plain_buffer(make):
@@ -444,7 +763,7 @@ def case_plain_buffer(make):
     assert out["prio_q"].shape == (0,) and out["weights"].shape == (0,)
 
 
-# ----------------------------------------------------------------------------- 5. refusals
+# ----------------------------------------------------------------------------- 7. refusals
 def case_refusals(nat, lib, host: bool):
     """The refusals of wh_replay_prio_*: codes of one library as a list (the caller compares the two
     libraries' lists).  On the host engine every pointer is a real sentinel-filled buffer that must
