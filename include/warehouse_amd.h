@@ -573,6 +573,79 @@ typedef struct wh_sac_td_args {
 } wh_sac_td_args;
 int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void* stream);
 
+/* SAC LOSSES: the critic, actor and alpha losses of RLlib's discrete SAC (sac_tf_policy, discrete
+ * branch) and d(loss)/d(logits), from the learner's own logits at `obs` (what wh_mlp_train_forward
+ * writes for the policy and the two Q networks) and the target y of wh_sac_td, which is a constant
+ * here.  For a live row r = m * NA + i, all in f32, sums over o = 0..8 in ascending order, no fused
+ * multiply-adds:
+ *   lse, logp[o], p[o] of pi[r] as in SAC TD TARGETS;  alpha = exp(log_alpha[0]);  w = weights[m]
+ *   a         = actions[m,i] if in 0..8 else 4
+ *   qm[o]     = min(q1[r,o], q2[r,o])                        (q2 NULL: q1 alone)
+ *   g[o]      = alpha * logp[o] - qm[o] ;  f = sum_o p[o] * g[o]               the actor row
+ *   dpi[r,j]  = (scale * p[j]) * (g[j] - f)
+ *   e_k       = qk[r,a] - y[r] ;  c_k = ((0.5 * w) * e_k) * e_k                the critic rows, k = 1, 2
+ *   dqk[r,o]  = (o == a) ? (scale * w) * e_k : 0
+ *   t         = sum_o p[o] * (logp[o] + target_entropy)                        the alpha row
+ * (d f / d pi[j] also holds alpha p[j] (1 - sum_o p[o]), which is 0 in exact arithmetic and is dropped.)
+ * The actor row is policy_t (alpha log_pis_t - stop_gradient(q_t)), the critic rows 0.5 MSE against y
+ * with the sampler's importance weights on them, the alpha row stop_gradient(policy_t) (-log_alpha
+ * stop_gradient(log_pis_t + target_entropy)).  The Huber critic loss of later RLlib versions is not
+ * built.  Rows i >= n[m] (n as in SAC TD TARGETS: NULL = NA, n[m] <= 0 = none) are dead: they write
+ * exact zeros to all three gradient arrays and add nothing to any sum.
+ *   stats[0] = scale * sum c_1      stats[1] = scale * sum c_2 (0 without q2)     stats[2] = scale * sum f
+ *   T = scale * sum t               stats[3] = (-log_alpha[0]) * T, the alpha loss
+ *   stats[4] = -T = d(alpha loss) / d(log_alpha)           stats[5] = the number of live rows, as f32
+ * `scale` is the caller's normaliser (a mean over all rows: 1 / (M * NA)); it is taken by value so that
+ * no pass over n has to count the live rows first, and stats[5] lets a caller renormalise.  log_alpha
+ * is read on the device: the call needs no host sync.  No atomics: every workgroup reduces its rows in
+ * a fixed order into `work`, and a second launch of one workgroup adds the workgroups' partial sums in a
+ * fixed order, so the result is a function of the inputs alone (at most 256 + workgroups additions
+ * deep; a batch of one workgroup is a single launch).  The host engine adds in ascending row order.
+ * stats[5] is exact up to 2^24 live rows.  `work` is scratch of wh_sac_loss_query's work_bytes (never
+ * 0), 16-byte aligned.  Neither entry point allocates or synchronises.  Inputs are assumed finite.
+ * WH_EINVAL: a == NULL, M < 0, NA outside 1 .. 16; and for M > 0: pi, q1, y, actions, log_alpha or
+ * stats NULL; dq2 set without q2; work NULL or not 16-byte aligned.  M = 0 launches nothing (WH_OK, no
+ * pointer looked at, stats untouched).  wh_sac_loss_query applies the rules of M and NA; work_bytes may
+ * be NULL.  Both engines implement both. */
+typedef struct wh_sac_loss_args {
+  const float *pi, *q1, *q2;        /* [M*NA, 9]; q2 may be NULL (no twin) */
+  const float* y;                   /* [M, NA] */
+  const int32_t* actions;           /* [M, NA] */
+  const int32_t* n;                 /* [M] or NULL */
+  const float* weights;             /* [M] or NULL (= 1) */
+  const float* log_alpha;           /* [1], device memory */
+  float target_entropy, scale;
+  float *dpi, *dq1, *dq2;           /* [M*NA, 9] out; any may be NULL */
+  float* stats;                     /* [6] out */
+  void* work;
+} wh_sac_loss_args;
+int wh_sac_loss_query(int64_t M, int32_t NA, int64_t* work_bytes);
+int wh_sac_loss(int64_t M, int32_t NA, const wh_sac_loss_args* a, void* stream);
+
+/* ADAM: one torch.optim.Adam step (no amsgrad, no weight decay, not maximize) over up to
+ * WH_ADAM_MAX_SEGS tensors in one launch.  `segs` is a host array that travels in the kernel
+ * argument: no table upload, no allocation, no sync.  The caller keeps the step count t and computes
+ * the hyper-parameters in double, rounding each once to f32.  Per element, in f32, in this order, no
+ * fused multiply-adds, sqrt and divide correctly rounded on both engines:
+ *   m' = beta1 * m + omb1 * g ;  v' = beta2 * v + (omb2 * g) * g
+ *   p' = p - step_size * (m' / (sqrt(v') / sqrt_bc2 + eps))
+ * so the two engines agree bit for bit.  p, m, v are updated in place.  Every pointer is 4-byte
+ * aligned; a segment whose four pointers are all 16-byte aligned moves 16 bytes per access.
+ * Overlapping segments are the caller's error and are not checked.
+ * WH_EINVAL: nseg outside 0 .. WH_ADAM_MAX_SEGS; h == NULL; for nseg > 0 segs == NULL; a segment with
+ * count < 0 or, for count > 0, a NULL or misaligned pointer.  nseg = 0 and segments of count 0 are
+ * WH_OK and touch nothing. */
+typedef struct wh_adam_seg { float *p, *m, *v; const float* g; int64_t count; } wh_adam_seg;
+typedef struct wh_adam_hyper {
+  float beta1, omb1;      /* beta1, 1 - beta1 */
+  float beta2, omb2;      /* beta2, 1 - beta2 */
+  float eps;
+  float step_size;        /* lr / (1 - beta1^t) */
+  float sqrt_bc2;         /* sqrt(1 - beta2^t) */
+} wh_adam_hyper;
+#define WH_ADAM_MAX_SEGS 24
+int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, void* stream);
+
 /* Library build identification (e.g. "warehouse_amd gfx950 <date>"). */
 const char* wh_version(void);
 

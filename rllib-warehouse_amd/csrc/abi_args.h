@@ -403,6 +403,48 @@ inline int sac_td_call(int64_t M, int32_t NA, const wh_sac_td_args* a) {
   return (a->mask_dones != 0 && !a->dones) ? WH_EINVAL : WH_OK;
 }
 
+// ----------------------------------------------------------------------------- SAC losses
+// wh_sac_loss / wh_sac_loss_query: the sizes first, then -- for M > 0 only -- the pointers.  A
+// workgroup (and the host engine's unit of `work`) owns floor(256 / NA) whole samples, like wh_sac_td;
+// `work` holds SAC_LOSS_PARTIALS floats per workgroup.
+constexpr int32_t SAC_LOSS_PARTIALS = 8;   // sum c1, sum c2, sum f, sum t, live rows, 3 unused (32 bytes)
+
+inline int64_t sac_loss_groups(int64_t M, int32_t NA) {
+  const int64_t spw = 256 / NA;
+  return (M + spw - 1) / spw;
+}
+
+inline int sac_loss_query_call(int64_t M, int32_t NA, int64_t* work_bytes) {
+  if (M < 0 || NA < 1 || NA > SAC_MAX_AGENTS) return WH_EINVAL;
+  const int64_t groups = sac_loss_groups(M, NA);
+  if (work_bytes) *work_bytes = (groups > 0 ? groups : 1) * SAC_LOSS_PARTIALS * (int64_t)sizeof(float);
+  return WH_OK;
+}
+
+inline int sac_loss_call(int64_t M, int32_t NA, const wh_sac_loss_args* a) {
+  if (!a || M < 0 || NA < 1 || NA > SAC_MAX_AGENTS) return WH_EINVAL;
+  if (M == 0) return WH_OK;
+  if (!a->pi || !a->q1 || !a->y || !a->actions || !a->log_alpha || !a->stats) return WH_EINVAL;
+  if (a->dq2 && !a->q2) return WH_EINVAL;
+  return (!a->work || ((uintptr_t)a->work & 15u)) ? WH_EINVAL : WH_OK;
+}
+
+// ----------------------------------------------------------------------------- Adam
+// wh_adam_step: the count of segments, h, segs, then every segment: its count, and for count > 0 its
+// four pointers, each 4-byte aligned.
+inline int adam_call(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h) {
+  if (nseg < 0 || nseg > WH_ADAM_MAX_SEGS || !h) return WH_EINVAL;
+  if (nseg > 0 && !segs) return WH_EINVAL;
+  for (int32_t s = 0; s < nseg; ++s) {
+    const wh_adam_seg& g = segs[s];
+    if (g.count < 0) return WH_EINVAL;
+    if (g.count == 0) continue;
+    if (!g.p || !g.m || !g.v || !g.g) return WH_EINVAL;
+    if (((uintptr_t)g.p | (uintptr_t)g.m | (uintptr_t)g.v | (uintptr_t)g.g) & 3u) return WH_EINVAL;
+  }
+  return WH_OK;
+}
+
 // ----------------------------------------------------------------------------- MLP training
 // wh_mlp_train_query / wh_mlp_train_forward / wh_mlp_backward, in the header's order: the desc, its
 // shape, its precision, rows < 0, the pointers, the alignment of `work`, the empty batch, the row limit.

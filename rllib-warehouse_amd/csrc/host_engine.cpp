@@ -968,6 +968,58 @@ int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void*) {
   return WH_OK;
 }
 
+// ---- SAC losses (include/warehouse_amd.h, SAC LOSSES): sac_formula.h's row arithmetic, the sums in
+// ascending row order; `work` is checked like the device's and not used
+int wh_sac_loss_query(int64_t M, int32_t NA, int64_t* work_bytes) { return wh_abi::sac_loss_query_call(M, NA, work_bytes); }
+
+int wh_sac_loss(int64_t M, int32_t NA, const wh_sac_loss_args* a, void*) {
+  const int rc = wh_abi::sac_loss_call(M, NA, a);
+  if (rc || M == 0) return rc;
+  const bool twin = a->q2 != nullptr;
+  const float alpha = expf(a->log_alpha[0]);
+  float sums[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  for (int64_t m = 0; m < M; ++m) {
+    const int nn = wh_sac::live_rows(a->n, m, NA);
+    const float w = a->weights ? a->weights[m] : 1.0f;
+    for (int i = 0; i < NA; ++i) {
+      const int64_t row = m * NA + i, e = row * wh_sac::OUT;
+      float dpi[wh_sac::OUT] = {};
+      float d1 = 0.0f, d2 = 0.0f;
+      int act = -1;
+      if (i < nn) {
+        act = wh_sac::taken_action(a->actions[row]);
+        const wh_sac::LossRow r = wh_sac::loss_row(a->pi + e, a->q1 + e, twin ? a->q2 + e : nullptr, twin, a->y[row], act,
+                                                   w, alpha, a->target_entropy, a->scale, dpi);
+        d1 = wh_sac::loss_dq(a->scale, w, r.e1);
+        d2 = twin ? wh_sac::loss_dq(a->scale, w, r.e2) : 0.0f;
+        sums[0] += r.c1;
+        sums[1] += r.c2;
+        sums[2] += r.f;
+        sums[3] += r.t;
+        sums[4] += 1.0f;
+      }
+      for (int o = 0; o < wh_sac::OUT; ++o) {
+        if (a->dpi) a->dpi[e + o] = dpi[o];
+        if (a->dq1) a->dq1[e + o] = o == act ? d1 : 0.0f;
+        if (a->dq2) a->dq2[e + o] = o == act ? d2 : 0.0f;
+      }
+    }
+  }
+  wh_sac::loss_stats(sums, a->scale, a->log_alpha[0], a->stats);
+  return WH_OK;
+}
+
+// ---- Adam (include/warehouse_amd.h, ADAM): sac_formula.h's element, segment after segment
+int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, void*) {
+  const int rc = wh_abi::adam_call(nseg, segs, h);
+  if (rc) return rc;
+  for (int32_t s = 0; s < nseg; ++s) {
+    const wh_adam_seg& g = segs[s];
+    for (int64_t e = 0; e < g.count; ++e) wh_sac::adam_element(*h, g.g[e], g.p[e], g.m[e], g.v[e]);
+  }
+  return WH_OK;
+}
+
 // ---- what the CPU has no use for: the policy network and its fragment operand (device formats),
 // the two-stream sampler step, prepared launches, assert-mode counters, and the 16-lanes-per-env
 // form (csrc/step_wide.h: the host engine has no lanes)

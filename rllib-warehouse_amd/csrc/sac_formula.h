@@ -66,4 +66,85 @@ WH_SAC_HD inline int live_rows(const int32_t* n, int64_t m, int NA) {
 // td[m] from the sum of its live rows' errors
 WH_SAC_HD inline float td_mean(float sum, int live) { return live > 0 ? sum / (float)live : 0.0f; }
 
+// ---- wh_sac_loss (include/warehouse_amd.h, SAC LOSSES)
+// what a live row adds to the four sums, and the TD errors its two critic gradients are made of
+struct LossRow {
+  float c1, c2, f, t;   // c2 = 0 without a twin
+  float e1, e2;         // qk[r,a] - y; e2 = 0 without a twin
+};
+
+// One live row: pi / q1 / q2 its nine logits (q2 is read only when `twin`), `a` the taken action 0..8,
+// w the importance weight.  dpi[9] receives (scale p[j]) (g[j] - f).  lse, logp and p as in soft_value.
+WH_SAC_HD inline LossRow loss_row(const float* pi, const float* q1, const float* q2, bool twin, float y, int a, float w,
+                                  float alpha, float target_entropy, float scale, float* dpi) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  float zmax = pi[0];
+  for (int o = 1; o < OUT; ++o) zmax = pi[o] > zmax ? pi[o] : zmax;
+  float s = 0.0f;
+  for (int o = 0; o < OUT; ++o) s += expf(pi[o] - zmax);
+  const float lse = zmax + logf(s);
+  float p[OUT], g[OUT];
+  LossRow r{};
+  float q1a = 0.0f, q2a = 0.0f;   // qk[a], by comparison: no indexing by a value known only at run time
+  for (int o = 0; o < OUT; ++o) {
+    const float logp = pi[o] - lse;
+    p[o] = expf(logp);
+    const float qm = (twin && q2[o] < q1[o]) ? q2[o] : q1[o];
+    g[o] = alpha * logp - qm;
+    r.f += p[o] * g[o];
+    r.t += p[o] * (logp + target_entropy);
+    if (o == a) {
+      q1a = q1[o];
+      q2a = twin ? q2[o] : 0.0f;
+    }
+  }
+  for (int j = 0; j < OUT; ++j) dpi[j] = (scale * p[j]) * (g[j] - r.f);
+  r.e1 = q1a - y;
+  r.c1 = ((0.5f * w) * r.e1) * r.e1;
+  if (twin) {
+    r.e2 = q2a - y;
+    r.c2 = ((0.5f * w) * r.e2) * r.e2;
+  }
+  return r;
+}
+
+// dqk[r, a] of a live row
+WH_SAC_HD inline float loss_dq(float scale, float w, float e) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  return (scale * w) * e;
+}
+
+// stats[0..5] from the sums over the live rows: sum c1, sum c2, sum f, sum t, the live row count
+WH_SAC_HD inline void loss_stats(const float* sums, float scale, float log_alpha, float* stats) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float T = scale * sums[3];
+  stats[0] = scale * sums[0];
+  stats[1] = scale * sums[1];
+  stats[2] = scale * sums[2];
+  stats[3] = (-log_alpha) * T;
+  stats[4] = -T;
+  stats[5] = sums[4];
+}
+
+// ---- wh_adam_step (include/warehouse_amd.h, ADAM): one element; sqrtf and / are correctly rounded
+// (H: wh_adam_hyper)
+template <class H>
+WH_SAC_HD inline void adam_element(const H& h, float g, float& p, float& m, float& v) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float m1 = h.beta1 * m + h.omb1 * g;
+  const float v1 = h.beta2 * v + (h.omb2 * g) * g;
+  const float denom = sqrtf(v1) / h.sqrt_bc2 + h.eps;
+  p = p - h.step_size * (m1 / denom);
+  m = m1;
+  v = v1;
+}
+
 }  // namespace wh_sac

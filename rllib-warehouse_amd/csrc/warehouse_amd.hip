@@ -59,6 +59,8 @@ namespace {
 #include "step_record.h"    // RecordParams, k_step_record: the recorded step (wh_replay_record)
 #include "prio.h"           // k_prio_fill, k_prio_update, k_prio_sample
 #include "sac.h"            // k_sac_td (the row arithmetic: sac_formula.h, shared with the host engine)
+#include "sac_loss.h"       // k_sac_loss, k_sac_loss_finish (after sac.h: its span constants)
+#include "adam.h"           // k_adam
 #include "sampler.h"        // FImg, SampLds, write_image, k_sampler
 #include "pack.h"           // k_pack, k_unpack
 
@@ -958,6 +960,44 @@ int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void* stream) {
   if (groups > 0x7FFFFFFF) return WH_EINVAL;
   const SacParams p{*a, M, NA, spw};
   hipLaunchKernelGGL(k_sac_td, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p);
+  return hip_err(hipGetLastError());
+}
+
+// ---- SAC losses (csrc/sac_loss.h): one launch, and for more than one workgroup the launch that adds
+// their partial sums
+int wh_sac_loss_query(int64_t M, int32_t NA, int64_t* work_bytes) { return wh_abi::sac_loss_query_call(M, NA, work_bytes); }
+
+int wh_sac_loss(int64_t M, int32_t NA, const wh_sac_loss_args* a, void* stream) {
+  const int rc = wh_abi::sac_loss_call(M, NA, a);
+  if (rc || M == 0) return rc;
+  const int64_t groups = wh_abi::sac_loss_groups(M, NA);
+  if (groups > 0x7FFFFFFF) return WH_EINVAL;
+  const SacLossParams p{*a, M, NA, BT / NA};
+  hipLaunchKernelGGL(k_sac_loss, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p);
+  if (groups > 1) {
+    const SacLossFinishParams f{static_cast<const float*>(a->work), groups, a->log_alpha, a->scale, a->stats};
+    hipLaunchKernelGGL(k_sac_loss_finish, dim3(1), dim3(BT), 0, (hipStream_t)stream, f);
+  }
+  return hip_err(hipGetLastError());
+}
+
+// ---- Adam (csrc/adam.h): the segment table and every segment's first workgroup go in the argument
+int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, void* stream) {
+  const int rc = wh_abi::adam_call(nseg, segs, h);
+  if (rc || nseg == 0) return rc;
+  AdamParams p{};
+  int64_t groups = 0;
+  for (int32_t s = 0; s < nseg; ++s) {
+    p.seg[s] = segs[s];
+    p.start[s] = (uint32_t)groups;
+    groups += (segs[s].count + ADAM_CHUNK - 1) / ADAM_CHUNK;
+    if (groups > 0x7FFFFFFF) return WH_EINVAL;
+  }
+  p.start[nseg] = (uint32_t)groups;
+  p.h = *h;
+  p.nseg = nseg;
+  if (groups == 0) return WH_OK;
+  hipLaunchKernelGGL(k_adam, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p);
   return hip_err(hipGetLastError());
 }
 

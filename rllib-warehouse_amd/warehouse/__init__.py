@@ -16,11 +16,13 @@ from .replay import ReplayBuffer  # noqa: F401
 from .sac import QNetwork, SACCritic  # noqa: F401
 from .policy import forward_many, policy_collect  # noqa: F401
 from .train import MLPTrainer, mlp_logits  # noqa: F401
+from .learner import DeviceAdam, SACLearner, sac_losses  # noqa: F401
 
 __all__ = []
 __all__.extend(core.__all__)
 __all__.extend(variants.__all__)
 __all__ += ["BatchedWarehouse", "EpisodeStats", "WarehouseVectorEnv", "WarehouseBaseEnv", "ReplayBuffer",
-            "SACCritic", "QNetwork", "forward_many", "policy_collect", "MLPTrainer", "mlp_logits"]
+            "SACCritic", "QNetwork", "forward_many", "policy_collect", "MLPTrainer", "mlp_logits",
+            "SACLearner", "DeviceAdam", "sac_losses"]
 
 name = "warehouse"

@@ -49,7 +49,8 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_replay_put", "wh_replay_gather", "wh_replay_record",
            "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample",
            "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi",
-           "wh_mlp_train_query", "wh_mlp_train_forward", "wh_mlp_backward")
+           "wh_mlp_train_query", "wh_mlp_train_forward", "wh_mlp_backward",
+           "wh_sac_loss_query", "wh_sac_loss", "wh_adam_step")
 
 WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
 WH_PRIO_MAX = 0x7FFFFFFF       # the largest stored priority
@@ -148,6 +149,29 @@ class WhSacTdArgs(ctypes.Structure):
                 [(k, ctypes.c_void_p) for k in ("y", "td_rows", "td")])
 
 
+class WhSacLossArgs(ctypes.Structure):
+    _fields_ = ([(k, ctypes.c_void_p) for k in ("pi", "q1", "q2", "y", "actions", "n", "weights", "log_alpha")] +
+                [("target_entropy", ctypes.c_float), ("scale", ctypes.c_float)] +
+                [(k, ctypes.c_void_p) for k in ("dpi", "dq1", "dq2", "stats", "work")])
+
+
+WH_ADAM_MAX_SEGS = 24   # tensors of one wh_adam_step launch
+
+
+class WhAdamSeg(ctypes.Structure):
+    _fields_ = [("p", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("g", ctypes.c_void_p),
+                ("count", ctypes.c_int64)]
+
+
+class WhAdamHyper(ctypes.Structure):   # f32 values the caller computes in double and rounds once
+    _fields_ = [(k, ctypes.c_float) for k in ("beta1", "omb1", "beta2", "omb2", "eps", "step_size", "sqrt_bc2")]
+
+
+def adam_hyper(lr: float, beta1: float, beta2: float, eps: float, t: int) -> WhAdamHyper:
+    """wh_adam_hyper of step t >= 1 (torch.optim.Adam's bias corrections), computed in double."""
+    return WhAdamHyper(beta1, 1.0 - beta1, beta2, 1.0 - beta2, eps, lr / (1.0 - beta1 ** t), (1.0 - beta2 ** t) ** 0.5)
+
+
 class WarehouseNativeError(RuntimeError):
     pass
 
@@ -244,6 +268,9 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_mlp_train_query.argtypes = [_MD, _I64, ctypes.POINTER(ctypes.c_int64)]
     S.wh_mlp_train_forward.argtypes = [_MD, _MW, _I64, _P, _P, _P, _P, _P]
     S.wh_mlp_backward.argtypes = [_MD, _MW, _I64, _P, _P, _P, _P, _MW, _P, _P]
+    S.wh_sac_loss_query.argtypes = [_I64, _I32, ctypes.POINTER(ctypes.c_int64)]
+    S.wh_sac_loss.argtypes = [_I64, _I32, ctypes.POINTER(WhSacLossArgs), _P]
+    S.wh_adam_step.argtypes = [_I32, ctypes.POINTER(WhAdamSeg), ctypes.POINTER(WhAdamHyper), _P]
     S.wh_check_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), _I32]
     S.wh_rollout_prepare.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _P,
                                      ctypes.POINTER(ctypes.c_void_p)]

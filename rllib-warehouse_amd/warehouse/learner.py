@@ -1,0 +1,258 @@
+"""A whole SAC learner update on the device (include/warehouse_amd.h, SAC LOSSES and ADAM;
+csrc/sac_loss.h, csrc/adam.h).
+
+`sac_losses` turns the learner's own logits at `obs` and the TD target into the three losses and their
+d(loss)/d(logits) in one call; `DeviceAdam` steps up to 24 tensors in one launch; `SACLearner` strings
+everything the package has into one `update(batch)`:
+
+    pol_m, q1_m, q2_m = (torch.nn.Sequential(...).to("cuda") for _ in range(3))   # what weights_of accepts
+    critic = SACCritic(policy, q1, q2, q1_target, q2_target, alpha=1.0, gamma=0.99)
+    learner = SACLearner(pol_m, q1_m, q2_m, rollout_policy=policy, critic=critic,
+                         log_alpha=torch.zeros(1, device="cuda"))
+    batch = buf.sample(64, rows=True, fragments=True)
+    out = learner.update(batch)                           # stats [6], td [M], y [M, NA]
+    buf.update_priorities(batch["idx_out"], out["td"])
+
+One host sync remains in an update: wh_sac_td takes alpha by value, so `update` reads log_alpha back
+(4 bytes) to set `critic.alpha`.  Everything else is enqueued on the current stream.
+"""
+from __future__ import annotations
+
+import ctypes
+import math
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+from . import _native as nat
+from .batched import _check_out, require_device
+from .policy import NUM_ACTIONS, weights_of
+from .sac import SACCritic
+from .train import KEYS, MLPTrainer
+
+_buf: Dict[tuple, torch.Tensor] = {}
+_work_bytes: Dict[tuple, int] = {}
+
+
+def _own(device, k: str, shape, dt=torch.float32) -> torch.Tensor:
+    """A buffer sac_losses owns: one size kept per device and name (as SACCritic._own)."""
+    t = _buf.get((device, k))
+    if t is None or tuple(t.shape) != tuple(shape):
+        t = _buf[(device, k)] = torch.empty(shape, dtype=dt, device=device)
+    return t
+
+
+def loss_work_bytes(M: int, NA: int) -> int:
+    """wh_sac_loss_query: the bytes of `work` for M samples of NA agents (asked once per size)."""
+    if (M, NA) not in _work_bytes:
+        n = ctypes.c_int64()
+        nat.check(nat.lib().wh_sac_loss_query(M, NA, ctypes.byref(n)), "wh_sac_loss_query")
+        _work_bytes[(M, NA)] = int(n.value)
+    return _work_bytes[(M, NA)]
+
+
+def _arg(t, what: str, shape, dtype, device) -> torch.Tensor:
+    if not torch.is_tensor(t):
+        raise ValueError(f"{what} must be a tensor")
+    try:
+        return _check_out(t, shape, dtype, device)
+    except ValueError as e:
+        raise ValueError(f"{what}: {e}") from None
+
+
+def sac_losses(pi: torch.Tensor, q1: torch.Tensor, q2: Optional[torch.Tensor], y: torch.Tensor,
+               actions: torch.Tensor, *, log_alpha: torch.Tensor, target_entropy: float,
+               n: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+               scale: Optional[float] = None, out: Optional[Dict[str, torch.Tensor]] = None):
+    """wh_sac_loss on the current stream, no host sync.
+
+    pi, q1, q2: [M*NA, 9] float32 logits of the policy and the Q networks at `obs` (q2 None: no twin);
+    y: [M, NA] float32, SACCritic's target; actions: [M, NA] int32; n: [M] int32 or None; weights: [M]
+    float32 or None; log_alpha: a one-element float32 device tensor.  scale None = 1 / (M * NA).
+    Returns {"dpi", "dq1", "dq2" (None without q2), "stats" [6]}: buffers this module owns, overwritten
+    by the next call of the same size on the device -- or the caller's through `out` (any of the
+    keys).  stats = (critic loss 1, critic loss 2, actor loss, alpha loss, d(alpha loss)/d(log_alpha),
+    live rows).  ValueError for a wrong argument, before any native call."""
+    if not torch.is_tensor(y) or y.dim() != 2:
+        raise ValueError("y must be a [M, NA] tensor")
+    M, NA = (int(s) for s in y.shape)
+    if not 1 <= NA <= 16:
+        raise ValueError(f"y: 1 .. 16 agents, got {NA}")
+    dev, rows = y.device, M * NA
+    _arg(y, "y", (M, NA), torch.float32, dev)
+    _arg(pi, "pi", (rows, NUM_ACTIONS), torch.float32, dev)
+    _arg(q1, "q1", (rows, NUM_ACTIONS), torch.float32, dev)
+    if q2 is not None:
+        _arg(q2, "q2", (rows, NUM_ACTIONS), torch.float32, dev)
+    _arg(actions, "actions", (M, NA), torch.int32, dev)
+    if n is not None:
+        _arg(n, "n", (M,), torch.int32, dev)
+    if weights is not None:
+        _arg(weights, "weights", (M,), torch.float32, dev)
+    if not torch.is_tensor(log_alpha) or log_alpha.numel() != 1:
+        raise ValueError("log_alpha must be a one-element tensor")
+    _arg(log_alpha, "log_alpha", log_alpha.shape, torch.float32, dev)
+    keys = ("dpi", "dq1", "dq2", "stats") if q2 is not None else ("dpi", "dq1", "stats")
+    shapes = dict(dpi=(rows, NUM_ACTIONS), dq1=(rows, NUM_ACTIONS), dq2=(rows, NUM_ACTIONS), stats=(6,))
+    if out is not None:
+        if any(k not in keys for k in out):
+            raise ValueError(f"out: some of {keys}, got {sorted(out)}")
+        for k, v in out.items():
+            _arg(v, k, shapes[k], torch.float32, dev)
+    require_device(dev)
+    res = {k: (out[k] if out is not None and k in out else _own(dev, k, shapes[k])) for k in keys}
+    res.setdefault("dq2", None)
+    if M == 0:
+        res["stats"].zero_()
+        return res
+    work = _own(dev, "work", (loss_work_bytes(M, NA),), torch.uint8)
+    args = nat.WhSacLossArgs(pi.data_ptr(), q1.data_ptr(), nat.ptr(q2), y.data_ptr(), actions.data_ptr(), nat.ptr(n),
+                             nat.ptr(weights), log_alpha.data_ptr(), float(target_entropy),
+                             1.0 / rows if scale is None else float(scale), res["dpi"].data_ptr(),
+                             res["dq1"].data_ptr(), nat.ptr(res["dq2"]), res["stats"].data_ptr(), work.data_ptr())
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().wh_sac_loss(M, NA, ctypes.byref(args), nat.stream_of(dev)), "wh_sac_loss")
+    return res
+
+
+class DeviceAdam:
+    """torch.optim.Adam (no amsgrad, no weight decay, not maximize) over up to 24 tensors, one launch per
+    step (wh_adam_step).  The defaults are RLlib's SAC optimisers'.  `m` and `v` are torch tensors this
+    object owns; the tensors are updated in place."""
+
+    def __init__(self, tensors: Sequence[torch.Tensor], lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-8):
+        tensors = [t.detach() if torch.is_tensor(t) else t for t in tensors]
+        self.device = self._check(tensors, "tensors")
+        self.tensors: List[torch.Tensor] = tensors
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.m = [torch.zeros_like(t) for t in tensors]
+        self.v = [torch.zeros_like(t) for t in tensors]
+        self.t = 0
+        self._segs = None   # (the gradients' addresses, the wh_adam_seg array built for them)
+
+    @staticmethod
+    def _check(tensors, what: str):
+        if len(tensors) > nat.WH_ADAM_MAX_SEGS:
+            raise ValueError(f"{what}: at most {nat.WH_ADAM_MAX_SEGS} tensors in one launch, got {len(tensors)}")
+        for i, t in enumerate(tensors):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or \
+                    t.device != tensors[0].device:
+                raise ValueError(f"{what}[{i}]: contiguous float32 tensors on one device")
+        if tensors and torch.cuda.is_available() and tensors[0].device.type != "cuda":
+            raise ValueError(f"{what}: on {tensors[0].device}, the kernel takes tensors on a HIP device")
+        return require_device(tensors[0].device) if tensors else None
+
+    def step(self, grads: Sequence[torch.Tensor]) -> None:
+        """One Adam step from `grads` (one per tensor, its shape), on the current stream, no sync."""
+        grads = list(grads)
+        if len(grads) != len(self.tensors):
+            raise ValueError(f"grads: {len(self.tensors)} tensors, got {len(grads)}")
+        key = tuple(g.data_ptr() if torch.is_tensor(g) else None for g in grads)
+        if self._segs is None or self._segs[0] != key:
+            for i, (g, t) in enumerate(zip(grads, self.tensors)):
+                if not torch.is_tensor(g) or g.dtype != torch.float32 or not g.is_contiguous() or \
+                        g.device != t.device or g.numel() != t.numel():
+                    raise ValueError(f"grads[{i}]: a contiguous float32 tensor of {t.numel()} elements on {t.device}")
+            arr = (nat.WhAdamSeg * max(1, len(grads)))()
+            for i, (t, m, v, g) in enumerate(zip(self.tensors, self.m, self.v, grads)):
+                arr[i] = nat.WhAdamSeg(t.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr(), t.numel())
+            self._segs = (key, arr)
+        self.t += 1
+        if not grads:
+            return
+        h = nat.adam_hyper(self.lr, self.betas[0], self.betas[1], self.eps, self.t)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().wh_adam_step(len(grads), self._segs[1], ctypes.byref(h), nat.stream_of(self.device)),
+                      "wh_adam_step")
+
+    def state_dict(self) -> dict:
+        """Copies of the step count, the moments and the hyper-parameters, for a checkpoint."""
+        return dict(step=self.t, lr=self.lr, betas=self.betas, eps=self.eps, m=[x.clone() for x in self.m],
+                    v=[x.clone() for x in self.v])
+
+    def load_state_dict(self, state: dict) -> None:
+        if len(state["m"]) != len(self.m) or len(state["v"]) != len(self.v) or \
+                any(a.shape != b.shape for a, b in zip(list(state["m"]) + list(state["v"]), self.m + self.v)):
+            raise ValueError("load_state_dict: the moments do not match this optimiser's tensors")
+        for dst, src in zip(self.m + self.v, list(state["m"]) + list(state["v"])):
+            dst.copy_(src)
+        self.t = int(state["step"])
+        self.lr, self.eps = float(state["lr"]), float(state["eps"])
+        self.betas = (float(state["betas"][0]), float(state["betas"][1]))
+
+
+class SACLearner:
+    """RLlib's discrete SAC learner step on the device, from what the package already has.
+
+    `policy_module`, `q1_module`, `q2_module`: the Sequential(Linear, ReLU, Linear, ReLU, Linear)s that
+    `weights_of` accepts, float32 on one HIP device (q2_module None with a critic without a twin): the
+    master weights.  `rollout_policy`: the MLPPolicy the sampler runs, refreshed after every update.
+    `critic`: the SACCritic whose q1 / q2 blobs mirror the two Q modules; its policy, when it is not
+    `rollout_policy` itself (an f32 copy beside a bf16 sampler, say), is refreshed as well.  `log_alpha`: a one-element float32 device tensor, e.g. torch.zeros(1, device=...)
+    for RLlib's initial alpha of 1; it is a parameter and is stepped in place.  target_entropy, lr and
+    target_network_update_freq default to the experiment YAMLs'."""
+
+    def __init__(self, policy_module, q1_module, q2_module, *, rollout_policy, critic: SACCritic,
+                 log_alpha: torch.Tensor, target_entropy: float = 0.935, lr: float = 3e-4,
+                 target_network_update_freq: int = 8000):
+        if not isinstance(critic, SACCritic):
+            raise ValueError("SACLearner: critic is a SACCritic")
+        if (q2_module is None) != (critic.q2 is None):
+            raise ValueError("SACLearner: q2_module and the critic's q2 come together (both, or neither)")
+        self.modules = [m for m in (policy_module, q1_module, q2_module) if m is not None]
+        self.trainers = [MLPTrainer(m) for m in self.modules]
+        self.device = self.trainers[0].device
+        if any(t.device != self.device for t in self.trainers) or critic.device != self.device or \
+                rollout_policy.device != self.device:
+            raise ValueError("SACLearner: the modules, the rollout policy and the critic live on one device")
+        if not torch.is_tensor(log_alpha) or log_alpha.numel() != 1 or log_alpha.dtype != torch.float32 or \
+                log_alpha.device != self.device:
+            raise ValueError(f"SACLearner: log_alpha is a one-element float32 tensor on {self.device}")
+        if int(target_network_update_freq) < 1:
+            raise ValueError("SACLearner: target_network_update_freq >= 1")
+        self.rollout_policy, self.critic = rollout_policy, critic
+        # the blobs that mirror a module: the rollout policy (and the critic's, when it is another object),
+        # the critic's q1 / q2
+        self.packed = [(rollout_policy, policy_module), (critic.q1, q1_module)]
+        if critic.policy is not rollout_policy:
+            self.packed.append((critic.policy, policy_module))
+        if critic.q2 is not None:
+            self.packed.append((critic.q2, q2_module))
+        self.log_alpha = log_alpha.detach()
+        self.target_entropy = float(target_entropy)
+        self.target_network_update_freq = int(target_network_update_freq)
+        self.params = [weights_of(m)[k] for m in self.modules for k in KEYS]
+        self.adam = DeviceAdam(self.params + [self.log_alpha.view(1)], lr=lr)
+        self.updates = 0
+        self.grads: Optional[List[torch.Tensor]] = None   # the gradients of the last update, in self.adam's order
+
+    def update(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+        """One learner step from a ReplayBuffer.sample(..., rows=True) dict (plus fragments=True when the
+        critic's networks are bf16): critic.td, the three training forwards on batch["obs"], sac_losses
+        (importance weights from batch["weights"] when the ring is prioritized), the three backwards, ONE
+        Adam launch over the 18 parameter tensors and log_alpha (whose gradient is stats[4], in place),
+        the repack of the rollout policy and the critic's networks, and every target_network_update_freq
+        updates critic.sync_targets().  Returns {"stats" [6], "td" [M], "y" [M, NA]}; the caller does
+        buf.update_priorities(batch["idx_out"], out["td"]).  Reads log_alpha back once (the only sync)."""
+        if "obs" not in batch:
+            raise ValueError("SACLearner: the batch holds no obs rows (sample(rows=True))")
+        self.critic.alpha = math.exp(float(self.log_alpha.item()))
+        td = self.critic.td(batch)
+        M, NA = td["y"].shape
+        obs = batch["obs"].view(M * NA, -1)
+        logits = [t.forward(obs) for t in self.trainers]
+        loss = sac_losses(logits[0], logits[1], logits[2] if len(logits) > 2 else None, td["y"], batch["actions"],
+                          log_alpha=self.log_alpha, target_entropy=self.target_entropy, n=batch.get("n"),
+                          weights=batch.get("weights"))
+        grads = []
+        for t, k in zip(self.trainers, ("dpi", "dq1", "dq2")):
+            g = t.backward(loss[k])
+            grads += [g[kk] for kk in KEYS]
+        self.grads = grads + [loss["stats"][4:5]]
+        self.adam.step(self.grads)
+        for net, m in self.packed:
+            net.load_weights(weights_of(m))
+        self.updates += 1
+        if self.updates % self.target_network_update_freq == 0:
+            self.critic.sync_targets()
+        return dict(stats=loss["stats"], td=td["td"], y=td["y"])

@@ -15,11 +15,12 @@ batch into RLlib's discrete-SAC TD target `y`, the per-row TD errors and one TD 
     policy.load_weights(weights_of(policy_module))      # after the learner's optimiser step
     critic.sync_targets()                               # every target_network_update_freq steps
 
-The losses (critic, actor, alpha), d(loss)/d(logits), optimisers and soft target updates (tau < 1)
-are the learner's, in torch; it hands new parameters back with `MLPPolicy.load_weights`.  A network's
-own forward under autograd and its backward need not be torch's: `warehouse.mlp_logits(module, obs)`
-(warehouse/train.py) is Q(obs) or pi(obs) on the device in exact f32, read from the module's
-parameters, and fills `param.grad` on `loss.backward()`.
+Soft target updates (tau < 1) are the learner's, in torch; it hands new parameters back with
+`MLPPolicy.load_weights`.  A network's own forward under autograd and its backward need not be torch's:
+`warehouse.mlp_logits(module, obs)` (warehouse/train.py) is Q(obs) or pi(obs) on the device in exact
+f32, read from the module's parameters, and fills `param.grad` on `loss.backward()`.  The losses
+(critic, actor, alpha) with their d(loss)/d(logits), the optimiser step, and one `update(batch)` over
+all of it are warehouse/learner.py's (`sac_losses`, `DeviceAdam`, `SACLearner`).
 """
 from __future__ import annotations
 

@@ -13,7 +13,8 @@ no second, torch copy of the forward for autograd to see:
     q.load_weights(weights_of(q_module))                      # the device packer, same stream
 
 `mlp_logits` is a torch.autograd.Function over the six parameters; `MLPTrainer` is the same pair of
-calls without autograd, on buffers it owns.  Losses, d(loss)/d(logits) and optimisers remain torch's.
+calls without autograd, on buffers it owns.  Losses, d(loss)/d(logits) and the optimiser step on the
+device are warehouse/learner.py's.
 No gradient with respect to the observations is produced, and there is no double backward.
 """
 from __future__ import annotations
