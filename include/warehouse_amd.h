@@ -404,6 +404,41 @@ int wh_mlp_backward(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows,
                     const float* h0, const float* h1, const float* dlogits, const wh_mlp_grads* g,
                     void* work, void* stream);
 
+/* The training passes of several networks of ONE shape in one launch per product: up to
+ * WH_MLP_TRAIN_MAX_NETS jobs that share `d` and `rows` (one tile geometry, one slice count and one block
+ * count per product; jobs may share one obs) run side by side, each launch's workgroups being network
+ * 0's, then network 1's, ...  A SAC learner's policy, Q1 and Q2 passes at a few hundred rows are bound
+ * by dispatch and by the depth of their MFMA chains, not by bytes: three networks then take three
+ * launches forward (one per layer) and three backward (four above 512 rows, the last one adding the
+ * partial weight gradients of all networks) instead of nine and nine (twelve).
+ * For every job, h0, h1 and logits hold byte for byte what wh_mlp_train_forward writes for that job's
+ * arguments and the six gradients byte for byte what wh_mlp_backward writes: a workgroup runs the tile
+ * of the single-network launch on the same arguments.  `work` is wh_mlp_backward's (wh_mlp_train_query
+ * bytes, 16-byte aligned), one per job.  No allocation, no synchronisation, no atomics.
+ * Checked in this order before anything is launched (a refused call launches and writes nothing):
+ * d == NULL WH_EINVAL; a shape that is no variant's, out_dim != 9 or a precision other than WH_MLP_F32
+ * WH_ENOTSUP; rows < 0 or rows > WH_MLP_TRAIN_MAX_ROWS WH_EINVAL; nnets < 0, nnets >
+ * WH_MLP_TRAIN_MAX_NETS, or nnets > 0 with jobs == NULL, WH_EINVAL; then per job in ascending order the
+ * pointer rules of the single call -- forward: NULL among w's six pointers, obs, h0, h1, logits;
+ * backward: NULL among w's six pointers, obs, h0, h1, dlogits, g's six pointers, work, or work not
+ * 16-byte aligned -- WH_EINVAL; then two jobs with the same h0, the same h1 or the same logits
+ * (forward), or with the same work or the same pointer in the same field of g (backward), WH_EINVAL.
+ * nnets == 0 is WH_OK with nothing launched.  rows == 0 is WH_OK: the forward launches nothing, the
+ * backward writes zeros to every job's six gradients.  Device only. */
+#define WH_MLP_TRAIN_MAX_NETS 4
+typedef struct wh_mlp_train_job {
+  wh_mlp_weights w;        /* this network's parameters (device, nn.Linear layout) */
+  const float* obs;        /* [rows, in_dim]; jobs may share one obs */
+  float *h0, *h1, *logits; /* forward writes all three; backward reads h0, h1 (logits unused there) */
+  const float* dlogits;    /* backward only */
+  wh_mlp_grads g;          /* backward only */
+  void* work;              /* backward only: wh_mlp_train_query(d, rows) bytes, 16-byte aligned, one per job */
+} wh_mlp_train_job;
+int wh_mlp_train_forward_multi(const wh_mlp_desc* d, int32_t nnets, const wh_mlp_train_job* jobs,
+                               int64_t rows, void* stream);
+int wh_mlp_backward_multi(const wh_mlp_desc* d, int32_t nnets, const wh_mlp_train_job* jobs,
+                          int64_t rows, void* stream);
+
 /* REPLAY RING: off-policy transitions kept as packed states instead of observation rows (every row
  * is a function of the packed state: 265 bytes per Medium-8 transition against 5,289 as f32 rows).
  * A ring holds `capacity` slots; a slot is one time step of all B envs.  The buffers are device

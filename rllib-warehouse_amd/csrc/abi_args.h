@@ -493,6 +493,32 @@ inline int mlp_backward_call(const wh_mlp_desc* d, const wh_mlp_weights* w, int6
   return rows > WH_MLP_TRAIN_MAX_ROWS ? WH_EINVAL : WH_OK;
 }
 
+// wh_mlp_train_forward_multi / wh_mlp_backward_multi, in the header's order: the desc, its shape and
+// precision, rows, the count of jobs, every job's own pointers in ascending order (all jobs before any
+// pair is looked at), then the buffers two jobs would both write.  Reads jobs[0 .. nnets - 1] only.
+inline int mlp_train_multi_call(const wh_mlp_desc* d, int32_t nnets, const wh_mlp_train_job* jobs, int64_t rows,
+                                bool backward) {
+  if (!d) return WH_EINVAL;
+  if (!mlp_train_shape_ok(d) || d->precision != WH_MLP_F32) return WH_ENOTSUP;
+  if (rows < 0 || rows > WH_MLP_TRAIN_MAX_ROWS) return WH_EINVAL;
+  if (nnets < 0 || nnets > WH_MLP_TRAIN_MAX_NETS || (nnets > 0 && !jobs)) return WH_EINVAL;
+  for (int32_t i = 0; i < nnets; ++i) {
+    const wh_mlp_train_job& j = jobs[i];
+    if (!mlp_weights_ok(&j.w) || !j.obs || !j.h0 || !j.h1) return WH_EINVAL;
+    if (!backward && !j.logits) return WH_EINVAL;
+    if (backward && (!j.dlogits || !mlp_grads_ok(&j.g) || !j.work || (uintptr_t)j.work % 16 != 0)) return WH_EINVAL;
+  }
+  for (int32_t i = 1; i < nnets; ++i)
+    for (int32_t o = 0; o < i; ++o) {
+      const wh_mlp_train_job &a = jobs[o], &b = jobs[i];
+      if (!backward && (a.h0 == b.h0 || a.h1 == b.h1 || a.logits == b.logits)) return WH_EINVAL;
+      if (backward && (a.work == b.work || a.g.w0 == b.g.w0 || a.g.b0 == b.g.b0 || a.g.w1 == b.g.w1 ||
+                       a.g.b1 == b.g.b1 || a.g.w2 == b.g.w2 || a.g.b2 == b.g.b2))
+        return WH_EINVAL;
+    }
+  return WH_OK;
+}
+
 // the quantisation rule, one for both engines (plain C++: also device code)
 #if defined(__HIPCC__)
 __host__ __device__

@@ -1051,6 +1051,8 @@ int wh_mlp_train_forward(const wh_mlp_desc*, const wh_mlp_weights*, int64_t, con
                          void*) { return WH_ENOTSUP; }
 int wh_mlp_backward(const wh_mlp_desc*, const wh_mlp_weights*, int64_t, const float*, const float*, const float*,
                     const float*, const wh_mlp_grads*, void*, void*) { return WH_ENOTSUP; }
+int wh_mlp_train_forward_multi(const wh_mlp_desc*, int32_t, const wh_mlp_train_job*, int64_t, void*) { return WH_ENOTSUP; }
+int wh_mlp_backward_multi(const wh_mlp_desc*, int32_t, const wh_mlp_train_job*, int64_t, void*) { return WH_ENOTSUP; }
 int wh_check_read(uint64_t*, int32_t) { return WH_ENOTSUP; }
 int wh_step_wide(const wh_config*, int64_t, uint32_t*, const int32_t*, float*, uint8_t*, const int32_t*, int32_t*,
                  uint64_t, int64_t, int32_t, void*) { return WH_ENOTSUP; }

@@ -224,6 +224,97 @@ __global__ __launch_bounds__(THREADS) void k_train_reduce(Reduce r) {
   else r.gb[q][m] = s;
 }
 
+// ------------------------------------------------------------- several networks of one shape in one launch
+// wh_mlp_train_forward_multi / wh_mlp_backward_multi: the same product of up to MAX_NETS networks side by
+// side in one grid.  All networks share the geometry (`shape`: one M, N, K, ksplit and block count) and
+// differ in their five pointers only, so the argument carries the geometry once.  Workgroups
+// net * shape.blocks .. (net + 1) * shape.blocks - 1 are network net's; the index depends on blockIdx.x and
+// the argument only, so it is workgroup-uniform and the network's pointers are scalar loads from the
+// argument segment (no register array is indexed).  The workgroup then runs tile<KIND, G> on the Job a
+// single-network launch would have been given and with the block id it would have had: tile is a
+// function of those two alone, so every output is byte for byte the single-network launch's.
+constexpr int MAX_NETS = 4;
+
+struct NetPtrs {
+  const float* a;
+  const float* b;
+  float* c;
+  const float* aux;
+  float* gb;
+};
+
+struct MultiJob {
+  Job shape;              // the geometry of every network's product; its own five pointers are unused
+  NetPtrs net[MAX_NETS];
+  uint32_t nnets;
+};
+
+__device__ __forceinline__ Job job_of(const MultiJob& m, uint32_t net) {
+  const NetPtrs p = m.net[__builtin_amdgcn_readfirstlane(net)];
+  Job j = m.shape;
+  j.a = p.a; j.b = p.b; j.c = p.c; j.aux = p.aux; j.gb = p.gb;
+  return j;
+}
+
+// one product of every network: a forward layer, or the last weight gradient
+template <Kind KIND, class G>
+__global__ __launch_bounds__(THREADS) void k_train_multi(MultiJob m) {
+  __shared__ float lds_a[LDS_WORDS], lds_b[LDS_WORDS];
+  const uint32_t per = m.shape.blocks;
+  tile<KIND, G>(job_of(m, blockIdx.x / per), blockIdx.x % per, lds_a, lds_b);
+}
+
+// k_train_pair for every network: all the weight gradients' workgroups first (the deeper product), then
+// all the dH's
+template <class G>
+__global__ __launch_bounds__(THREADS) void k_train_pair_multi(MultiJob g, MultiJob d) {
+  __shared__ float lds_a[LDS_WORDS], lds_b[LDS_WORDS];
+  const uint32_t grad_blocks = g.nnets * g.shape.blocks;
+  if (blockIdx.x < grad_blocks) {
+    const uint32_t per = g.shape.blocks;
+    tile<GRAD, G>(job_of(g, blockIdx.x / per), blockIdx.x % per, lds_a, lds_b);
+  } else {
+    const uint32_t b = blockIdx.x - grad_blocks, per = d.shape.blocks;
+    tile<DH, G>(job_of(d, b / per), b % per, lds_a, lds_b);
+  }
+}
+
+// k_train_reduce over the three gradients of every network (up to 12): workgroups net * per ..
+// (net + 1) * per - 1, per = ceil(first[3] / THREADS), are network net's and walk its elements as
+// k_train_reduce's do.
+struct ReducePtrs {
+  const float* part[3];
+  float* gw[3];
+  float* gb[3];
+};
+
+struct ReduceMulti {
+  int64_t M[3], N[3];
+  int64_t first[4];
+  int32_t ksplit;
+  uint32_t per;           // workgroups per network
+  ReducePtrs net[MAX_NETS];
+};
+
+__global__ __launch_bounds__(THREADS) void k_train_reduce_multi(ReduceMulti r) {
+  const uint32_t net = __builtin_amdgcn_readfirstlane(blockIdx.x / r.per);
+  const int64_t e = (int64_t)(blockIdx.x % r.per) * THREADS + threadIdx.x;
+  if (e >= r.first[3]) return;
+  const ReducePtrs p = r.net[net];
+  // (the gradient index differs from thread to thread: selected by comparison, not by indexing)
+  const bool q2 = e >= r.first[2], q1 = e >= r.first[1];
+  const float* part = q2 ? p.part[2] : q1 ? p.part[1] : p.part[0];
+  float* gw = q2 ? p.gw[2] : q1 ? p.gw[1] : p.gw[0];
+  float* gb = q2 ? p.gb[2] : q1 ? p.gb[1] : p.gb[0];
+  const int64_t M = q2 ? r.M[2] : q1 ? r.M[1] : r.M[0], N = q2 ? r.N[2] : q1 ? r.N[1] : r.N[0];
+  const int64_t o = e - (q2 ? r.first[2] : q1 ? r.first[1] : r.first[0]), NT = N + 1, size = M * NT;
+  float s = part[o];
+  for (int k = 1; k < r.ksplit; ++k) s += part[k * size + o];
+  const int64_t m = o / NT, n = o % NT;
+  if (n < N) gw[m * N + n] = s;
+  else gb[m] = s;
+}
+
 // ------------------------------------------------------------------------------------------ host side
 struct Dims { int64_t in, h0, h1; };
 
@@ -319,6 +410,113 @@ inline int backward(const Dims& d, const wh_mlp_weights& w, int64_t rows, const 
                     const float* h1, const float* dz, const wh_mlp_grads& g, void* work, hipStream_t s) {
   return deep(rows) ? backward_on<Deep>(d, w, rows, obs, h0, h1, dz, g, work, s)
                     : backward_on<Wide>(d, w, rows, obs, h0, h1, dz, g, work, s);
+}
+
+// ---- several networks (wh_mlp_train_forward_multi, wh_mlp_backward_multi).  Every MultiJob is the Job
+// forward_on / backward_on make for one network (make_job with that network's pointers), the geometry
+// kept once.
+static_assert(MAX_NETS == WH_MLP_TRAIN_MAX_NETS, "mlp_train.h and the header agree on the network limit");
+
+// network i's slices of `work`, as backward_on lays them out
+struct Work {
+  float *dh1, *dh0, *part2, *part1, *part0;
+};
+
+inline Work work_of(const Dims& d, int64_t rows, void* work) {
+  const int64_t ks = ksplit_of(rows);
+  Work w;
+  w.dh1 = static_cast<float*>(work);
+  w.dh0 = w.dh1 + rows * d.h1;
+  w.part2 = w.dh0 + rows * d.h0;
+  w.part1 = w.part2 + ks * 9 * (d.h1 + 1);
+  w.part0 = w.part1 + ks * d.h1 * (d.h0 + 1);
+  return w;
+}
+
+inline MultiJob make_multi(int T, Kind kind, int n, const NetPtrs* p, int64_t lda, int64_t ldb, int64_t M, int64_t N,
+                           int64_t K, int64_t ksplit) {
+  MultiJob m{};
+  m.shape = make_job(T, kind, nullptr, lda, nullptr, ldb, nullptr, nullptr, nullptr, M, N, K, ksplit);
+  for (int i = 0; i < n; ++i) m.net[i] = p[i];
+  m.nnets = (uint32_t)n;
+  return m;
+}
+
+template <Kind KIND, class G>
+inline void launch_multi(const MultiJob& m, hipStream_t s) {
+  if (m.nnets * m.shape.blocks)
+    hipLaunchKernelGGL((k_train_multi<KIND, G>), dim3(m.nnets * m.shape.blocks), dim3(THREADS), 0, s, m);
+}
+
+template <class G>
+inline int forward_multi_on(const Dims& d, int n, const wh_mlp_train_job* jobs, int64_t rows, hipStream_t s) {
+  constexpr int T = G::T;
+  NetPtrs p[MAX_NETS];
+  for (int i = 0; i < n; ++i) p[i] = NetPtrs{jobs[i].obs, jobs[i].w.w0, jobs[i].h0, jobs[i].w.b0, nullptr};
+  launch_multi<FWD_RELU, G>(make_multi(T, FWD_RELU, n, p, d.in, d.in, rows, d.h0, d.in, 1), s);
+  for (int i = 0; i < n; ++i) p[i] = NetPtrs{jobs[i].h0, jobs[i].w.w1, jobs[i].h1, jobs[i].w.b1, nullptr};
+  launch_multi<FWD_RELU, G>(make_multi(T, FWD_RELU, n, p, d.h0, d.h0, rows, d.h1, d.h0, 1), s);
+  for (int i = 0; i < n; ++i) p[i] = NetPtrs{jobs[i].h1, jobs[i].w.w2, jobs[i].logits, jobs[i].w.b2, nullptr};
+  launch_multi<FWD_LINEAR, G>(make_multi(T, FWD_LINEAR, n, p, d.h1, d.h1, rows, 9, d.h1, 1), s);
+  return hip_rc(hipGetLastError());
+}
+
+inline int forward_multi(const Dims& d, int n, const wh_mlp_train_job* jobs, int64_t rows, hipStream_t s) {
+  return deep(rows) ? forward_multi_on<Deep>(d, n, jobs, rows, s) : forward_multi_on<Wide>(d, n, jobs, rows, s);
+}
+
+template <class G>
+inline int backward_multi_on(const Dims& d, int n, const wh_mlp_train_job* jobs, int64_t rows, hipStream_t s) {
+  constexpr int T = G::T;
+  const int64_t ks = ksplit_of(rows);
+  const bool split = ks > 1;
+  Work wk[MAX_NETS];
+  NetPtrs pg[MAX_NETS], pd[MAX_NETS];
+  for (int i = 0; i < n; ++i) wk[i] = work_of(d, rows, jobs[i].work);
+  // dH1 beside gW2, gb2
+  for (int i = 0; i < n; ++i) {
+    const wh_mlp_train_job& j = jobs[i];
+    pg[i] = NetPtrs{j.dlogits, j.h1, split ? wk[i].part2 : j.g.w2, nullptr, j.g.b2};
+    pd[i] = NetPtrs{j.dlogits, j.w.w2, wk[i].dh1, j.h1, nullptr};
+  }
+  const MultiJob g2 = make_multi(T, GRAD, n, pg, 9, d.h1, 9, d.h1, rows, ks);
+  const MultiJob d1 = make_multi(T, DH, n, pd, 9, d.h1, rows, d.h1, 9, 1);
+  hipLaunchKernelGGL(k_train_pair_multi<G>, dim3(n * (g2.shape.blocks + d1.shape.blocks)), dim3(THREADS), 0, s, g2, d1);
+  // dH0 beside gW1, gb1
+  for (int i = 0; i < n; ++i) {
+    const wh_mlp_train_job& j = jobs[i];
+    pg[i] = NetPtrs{wk[i].dh1, j.h0, split ? wk[i].part1 : j.g.w1, nullptr, j.g.b1};
+    pd[i] = NetPtrs{wk[i].dh1, j.w.w1, wk[i].dh0, j.h0, nullptr};
+  }
+  const MultiJob g1 = make_multi(T, GRAD, n, pg, d.h1, d.h0, d.h1, d.h0, rows, ks);
+  const MultiJob d0 = make_multi(T, DH, n, pd, d.h1, d.h0, rows, d.h0, d.h1, 1);
+  hipLaunchKernelGGL(k_train_pair_multi<G>, dim3(n * (g1.shape.blocks + d0.shape.blocks)), dim3(THREADS), 0, s, g1, d0);
+  // gW0, gb0
+  for (int i = 0; i < n; ++i) {
+    const wh_mlp_train_job& j = jobs[i];
+    pg[i] = NetPtrs{wk[i].dh0, j.obs, split ? wk[i].part0 : j.g.w0, nullptr, j.g.b0};
+  }
+  launch_multi<GRAD, G>(make_multi(T, GRAD, n, pg, d.h0, d.in, d.h0, d.in, rows, ks), s);
+  if (split) {
+    ReduceMulti r{};
+    const int64_t M[3] = {9, d.h1, d.h0}, N[3] = {d.h1, d.h0, d.in};
+    for (int q = 0; q < 3; ++q) {
+      r.M[q] = M[q]; r.N[q] = N[q];
+      r.first[q + 1] = r.first[q] + M[q] * (N[q] + 1);
+    }
+    r.ksplit = (int32_t)ks;
+    r.per = cdiv(r.first[3], THREADS);
+    for (int i = 0; i < n; ++i) {
+      const wh_mlp_grads& g = jobs[i].g;
+      r.net[i] = ReducePtrs{{wk[i].part2, wk[i].part1, wk[i].part0}, {g.w2, g.w1, g.w0}, {g.b2, g.b1, g.b0}};
+    }
+    hipLaunchKernelGGL(k_train_reduce_multi, dim3(n * r.per), dim3(THREADS), 0, s, r);
+  }
+  return hip_rc(hipGetLastError());
+}
+
+inline int backward_multi(const Dims& d, int n, const wh_mlp_train_job* jobs, int64_t rows, hipStream_t s) {
+  return deep(rows) ? backward_multi_on<Deep>(d, n, jobs, rows, s) : backward_multi_on<Wide>(d, n, jobs, rows, s);
 }
 
 }  // namespace train

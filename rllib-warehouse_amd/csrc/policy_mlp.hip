@@ -284,4 +284,18 @@ int wh_mlp_backward(const wh_mlp_desc* d, const wh_mlp_weights* w, int64_t rows,
                          (hipStream_t)stream);
 }
 
+int wh_mlp_train_forward_multi(const wh_mlp_desc* d, int32_t nnets, const wh_mlp_train_job* jobs, int64_t rows,
+                               void* stream) {
+  if (const int rc = wh_abi::mlp_train_multi_call(d, nnets, jobs, rows, false)) return rc;
+  if (nnets == 0 || rows == 0) return WH_OK;
+  return train::forward_multi(train::Dims{d->in_dim, d->hidden0, d->hidden1}, nnets, jobs, rows, (hipStream_t)stream);
+}
+
+int wh_mlp_backward_multi(const wh_mlp_desc* d, int32_t nnets, const wh_mlp_train_job* jobs, int64_t rows,
+                          void* stream) {
+  if (const int rc = wh_abi::mlp_train_multi_call(d, nnets, jobs, rows, true)) return rc;
+  if (nnets == 0) return WH_OK;
+  return train::backward_multi(train::Dims{d->in_dim, d->hidden0, d->hidden1}, nnets, jobs, rows, (hipStream_t)stream);
+}
+
 }  // extern "C"

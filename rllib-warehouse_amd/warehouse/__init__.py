@@ -15,7 +15,7 @@ from .vector import WarehouseBaseEnv, WarehouseVectorEnv  # noqa: F401
 from .replay import ReplayBuffer  # noqa: F401
 from .sac import QNetwork, SACCritic  # noqa: F401
 from .policy import forward_many, policy_collect  # noqa: F401
-from .train import MLPTrainer, mlp_logits  # noqa: F401
+from .train import MLPTrainer, mlp_logits, train_backward_many, train_forward_many  # noqa: F401
 from .learner import DeviceAdam, SACLearner, sac_losses  # noqa: F401
 
 __all__ = []

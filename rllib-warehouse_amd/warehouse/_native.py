@@ -50,6 +50,7 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_replay_prio_query", "wh_replay_prio_fill", "wh_replay_prio_update", "wh_replay_prio_sample",
            "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi",
            "wh_mlp_train_query", "wh_mlp_train_forward", "wh_mlp_backward",
+           "wh_mlp_train_forward_multi", "wh_mlp_backward_multi",
            "wh_sac_loss_query", "wh_sac_loss", "wh_adam_step")
 
 WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
@@ -140,6 +141,14 @@ class WhMlpWeights(ctypes.Structure):   # wh_mlp_weights and wh_mlp_grads: six d
 
 
 WhMlpGrads = WhMlpWeights
+
+WH_MLP_TRAIN_MAX_NETS = 4   # networks of one wh_mlp_train_forward_multi / wh_mlp_backward_multi call
+
+
+class WhMlpTrainJob(ctypes.Structure):   # wh_mlp_train_job
+    _fields_ = [("w", WhMlpWeights), ("obs", ctypes.c_void_p), ("h0", ctypes.c_void_p), ("h1", ctypes.c_void_p),
+                ("logits", ctypes.c_void_p), ("dlogits", ctypes.c_void_p), ("g", WhMlpGrads),
+                ("work", ctypes.c_void_p)]
 
 
 class WhSacTdArgs(ctypes.Structure):
@@ -268,6 +277,8 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_mlp_train_query.argtypes = [_MD, _I64, ctypes.POINTER(ctypes.c_int64)]
     S.wh_mlp_train_forward.argtypes = [_MD, _MW, _I64, _P, _P, _P, _P, _P]
     S.wh_mlp_backward.argtypes = [_MD, _MW, _I64, _P, _P, _P, _P, _MW, _P, _P]
+    S.wh_mlp_train_forward_multi.argtypes = [_MD, _I32, ctypes.POINTER(WhMlpTrainJob), _I64, _P]
+    S.wh_mlp_backward_multi.argtypes = [_MD, _I32, ctypes.POINTER(WhMlpTrainJob), _I64, _P]
     S.wh_sac_loss_query.argtypes = [_I64, _I32, ctypes.POINTER(ctypes.c_int64)]
     S.wh_sac_loss.argtypes = [_I64, _I32, ctypes.POINTER(WhSacLossArgs), _P]
     S.wh_adam_step.argtypes = [_I32, ctypes.POINTER(WhAdamSeg), ctypes.POINTER(WhAdamHyper), _P]

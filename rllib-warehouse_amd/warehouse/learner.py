@@ -28,7 +28,7 @@ from . import _native as nat
 from .batched import _check_out, require_device
 from .policy import NUM_ACTIONS, weights_of
 from .sac import SACCritic
-from .train import KEYS, MLPTrainer
+from .train import KEYS, MLPTrainer, train_backward_many, train_forward_many
 
 _buf: Dict[tuple, torch.Tensor] = {}
 _work_bytes: Dict[tuple, int] = {}
@@ -190,11 +190,24 @@ class SACLearner:
     `critic`: the SACCritic whose q1 / q2 blobs mirror the two Q modules; its policy, when it is not
     `rollout_policy` itself (an f32 copy beside a bf16 sampler, say), is refreshed as well.  `log_alpha`: a one-element float32 device tensor, e.g. torch.zeros(1, device=...)
     for RLlib's initial alpha of 1; it is a parameter and is stepped in place.  target_entropy, lr and
-    target_network_update_freq default to the experiment YAMLs'."""
+    target_network_update_freq default to the experiment YAMLs'.  `fused_train`: True runs the modules'
+    training passes in one launch per product for all of them (train_forward_many / train_backward_many),
+    False one module after the other, None (default) takes the fused route when the modules have one
+    shape and the batch has at most FUSED_TRAIN_MAX_ROWS agent rows; `update()` returns the same bytes
+    either way.  `last_fused_train` says which route the last update took."""
+
+    # fused_train=None takes the fused route up to this many agent rows (M x NA): the largest batch at which
+    # it measured faster by more than the spread of the sequential route's rounds.  SACLearner.update on
+    # one MI355X, fused / sequential in us (DESIGN.md §5.15, profiles/mlp_train_multi_probe.txt): Small-4
+    # 256 rows 273.6 / 306.8, 2,048 rows 303.8 / 430.2; Medium-8 512 rows 288.8 / 326.8, 4,096 rows 523.0 /
+    # 697.8.  Nothing above 4,096 rows was measured, so nothing above takes the fused route unasked.
+    FUSED_TRAIN_MAX_ROWS = 4096
 
     def __init__(self, policy_module, q1_module, q2_module, *, rollout_policy, critic: SACCritic,
                  log_alpha: torch.Tensor, target_entropy: float = 0.935, lr: float = 3e-4,
-                 target_network_update_freq: int = 8000):
+                 target_network_update_freq: int = 8000, fused_train: Optional[bool] = None):
+        if fused_train is not None and not isinstance(fused_train, bool):
+            raise ValueError(f"SACLearner: fused_train is True, False or None, got {fused_train!r}")
         if not isinstance(critic, SACCritic):
             raise ValueError("SACLearner: critic is a SACCritic")
         if (q2_module is None) != (critic.q2 is None):
@@ -202,6 +215,11 @@ class SACLearner:
         self.modules = [m for m in (policy_module, q1_module, q2_module) if m is not None]
         self.trainers = [MLPTrainer(m) for m in self.modules]
         self.device = self.trainers[0].device
+        self.one_shape = all(t.dims == self.trainers[0].dims for t in self.trainers)
+        if fused_train and not self.one_shape:
+            raise ValueError("SACLearner: fused_train=True takes modules of one shape")
+        self.fused_train = fused_train
+        self.last_fused_train: Optional[bool] = None
         if any(t.device != self.device for t in self.trainers) or critic.device != self.device or \
                 rollout_policy.device != self.device:
             raise ValueError("SACLearner: the modules, the rollout policy and the critic live on one device")
@@ -226,10 +244,17 @@ class SACLearner:
         self.updates = 0
         self.grads: Optional[List[torch.Tensor]] = None   # the gradients of the last update, in self.adam's order
 
+    def use_fused_train(self, rows: int) -> bool:
+        """Whether an update over `rows` agent rows runs the modules' training passes fused."""
+        if self.fused_train is None:
+            return self.one_shape and rows <= self.FUSED_TRAIN_MAX_ROWS
+        return self.fused_train
+
     def update(self, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         """One learner step from a ReplayBuffer.sample(..., rows=True) dict (plus fragments=True when the
         critic's networks are bf16): critic.td, the three training forwards on batch["obs"], sac_losses
-        (importance weights from batch["weights"] when the ring is prioritized), the three backwards, ONE
+        (importance weights from batch["weights"] when the ring is prioritized), the three backwards (the
+        forwards and the backwards each in one launch per product for all modules on the fused route), ONE
         Adam launch over the 18 parameter tensors and log_alpha (whose gradient is stats[4], in place),
         the repack of the rollout policy and the critic's networks, and every target_network_update_freq
         updates critic.sync_targets().  Returns {"stats" [6], "td" [M], "y" [M, NA]}; the caller does
@@ -240,14 +265,20 @@ class SACLearner:
         td = self.critic.td(batch)
         M, NA = td["y"].shape
         obs = batch["obs"].view(M * NA, -1)
-        logits = [t.forward(obs) for t in self.trainers]
+        fused = self.last_fused_train = self.use_fused_train(M * NA)
+        if fused:
+            logits = train_forward_many(self.trainers, obs)
+        else:
+            logits = [t.forward(obs) for t in self.trainers]
         loss = sac_losses(logits[0], logits[1], logits[2] if len(logits) > 2 else None, td["y"], batch["actions"],
                           log_alpha=self.log_alpha, target_entropy=self.target_entropy, n=batch.get("n"),
                           weights=batch.get("weights"))
-        grads = []
-        for t, k in zip(self.trainers, ("dpi", "dq1", "dq2")):
-            g = t.backward(loss[k])
-            grads += [g[kk] for kk in KEYS]
+        dz = [loss[k] for _, k in zip(self.trainers, ("dpi", "dq1", "dq2"))]
+        if fused:
+            per_net = train_backward_many(self.trainers, dz)
+        else:
+            per_net = [t.backward(d) for t, d in zip(self.trainers, dz)]
+        grads = [g[kk] for g in per_net for kk in KEYS]
         self.grads = grads + [loss["stats"][4:5]]
         self.adam.step(self.grads)
         for net, m in self.packed:

@@ -13,7 +13,9 @@ no second, torch copy of the forward for autograd to see:
     q.load_weights(weights_of(q_module))                      # the device packer, same stream
 
 `mlp_logits` is a torch.autograd.Function over the six parameters; `MLPTrainer` is the same pair of
-calls without autograd, on buffers it owns.  Losses, d(loss)/d(logits) and the optimiser step on the
+calls without autograd, on buffers it owns; `train_forward_many` / `train_backward_many` run up to four
+trainers of one shape in one launch per product (wh_mlp_train_forward_multi / wh_mlp_backward_multi),
+with the bytes of the trainers' own calls.  Losses, d(loss)/d(logits) and the optimiser step on the
 device are warehouse/learner.py's.
 No gradient with respect to the observations is produced, and there is no double backward.
 """
@@ -249,3 +251,117 @@ class MLPTrainer:
         work = self._own("work", (work_bytes(self.dims, rows),), torch.uint8)
         _run_backward(self.dims, w, obs, h0, h1, dlogits, grads, work)
         return grads
+
+
+# ------------------------------------------------------------------ several trainers in one launch per product
+def _check_many(trainers, what: str):
+    """The list itself: MLPTrainers, at most WH_MLP_TRAIN_MAX_NETS, none twice, one shape, one device."""
+    trainers = list(trainers)
+    if len(trainers) > nat.WH_MLP_TRAIN_MAX_NETS:
+        raise ValueError(f"{what}: at most {nat.WH_MLP_TRAIN_MAX_NETS} trainers in one call, got {len(trainers)}")
+    for i, t in enumerate(trainers):
+        if not isinstance(t, MLPTrainer):
+            raise ValueError(f"{what}: trainers[{i}] is no MLPTrainer")
+        if any(t is o for o in trainers[:i]):
+            raise ValueError(f"{what}: trainers[{i}] is listed twice (its buffers would be written twice)")
+        if t.dims != trainers[0].dims:
+            raise ValueError(f"{what}: one network shape per call, got {trainers[0].dims} and {t.dims}")
+        if t.device != trainers[0].device:
+            raise ValueError(f"{what}: one device per call, got {trainers[0].device} and {t.device}")
+    return trainers
+
+
+def _run_many(name: str, dims, device, jobs, rows: int) -> None:
+    arr = (nat.WhMlpTrainJob * len(jobs))(*jobs)
+    desc = _desc(dims)
+    with torch.cuda.device(device):
+        nat.check(getattr(nat.lib(), name)(ctypes.byref(desc), len(jobs), arr, rows, nat.stream_of(device)), name)
+
+
+def train_forward_many(trainers, obs):
+    """`[t.forward(o) for t, o in zip(trainers, obs)]` in three launches for all trainers
+    (wh_mlp_train_forward_multi) instead of three each: the same bytes in the same buffers.
+
+    `trainers`: up to four MLPTrainers of one shape on one device, none twice.  `obs`: one [rows, in_dim]
+    tensor for all of them, or a list of one per trainer, all of one row count.  Every trainer keeps its
+    obs, h0 / h1 and logits as its own forward() does, so `activations()` and a later `backward()` -- its
+    own or train_backward_many -- work as after its own forward().  Returns the trainers' logits.  An
+    empty list returns an empty list.  ValueError for a bad argument, before any native call."""
+    trainers = _check_many(trainers, "train_forward_many")
+    if torch.is_tensor(obs):
+        obs = [obs] * len(trainers)
+    else:
+        obs = list(obs)
+        if len(obs) != len(trainers):
+            raise ValueError(f"train_forward_many: obs is one tensor or one per trainer ({len(trainers)}), got {len(obs)}")
+    if not trainers:
+        return []
+    dims, dev = trainers[0].dims, trainers[0].device
+    ws = [t._weights() for t in trainers]
+    rows = [_check_obs(o, dims, dev) for o in obs]
+    if any(r != rows[0] for r in rows):
+        raise ValueError(f"train_forward_many: one row count per call, got {rows}")
+    jobs, outs = [], []
+    for t, w, o in zip(trainers, ws, obs):
+        out = t._own("logits", (rows[0], NUM_ACTIONS))
+        h0, h1 = t._own("h0", (rows[0], dims[1])), t._own("h1", (rows[0], dims[2]))
+        jobs.append(nat.WhMlpTrainJob(_struct(w), _ptr(o), _ptr(h0), _ptr(h1), _ptr(out), None,
+                                      nat.WhMlpGrads(), None))
+        outs.append(out)
+    if rows[0] > 0:       # (no rows: nothing to launch, and the shared placeholder address is no two buffers)
+        _run_many("wh_mlp_train_forward_multi", dims, dev, jobs, rows[0])
+    for t, o in zip(trainers, obs):
+        t._obs = o
+    return outs
+
+
+def train_backward_many(trainers, dlogits, out=None):
+    """`[t.backward(dz, out=o) for ...]` in three launches for all trainers (four above 512 rows;
+    wh_mlp_backward_multi): the same bytes in the same buffers.
+
+    `trainers` as for train_forward_many, each after a forward of one row count; `dlogits`: a list of one
+    [rows, 9] tensor per trainer; `out`: None, or a list of one dict of six tensors (or None: the
+    trainer's own) per trainer.  Returns the list of gradient dicts.  An empty list returns an empty
+    list.  ValueError for a bad argument, before any native call."""
+    trainers = _check_many(trainers, "train_backward_many")
+    if torch.is_tensor(dlogits):
+        raise ValueError("train_backward_many: dlogits is a list of one tensor per trainer")
+    dlogits = list(dlogits)
+    if len(dlogits) != len(trainers):
+        raise ValueError(f"train_backward_many: {len(trainers)} dlogits, got {len(dlogits)}")
+    outs = [None] * len(trainers) if out is None else list(out)
+    if len(outs) != len(trainers):
+        raise ValueError(f"train_backward_many: out is None or one entry per trainer ({len(trainers)}), got {len(outs)}")
+    if not trainers:
+        return []
+    dims, dev = trainers[0].dims, trainers[0].device
+    for i, t in enumerate(trainers):
+        if t._obs is None:
+            raise ValueError(f"train_backward_many: trainers[{i}] has had no forward yet")
+    rows = [int(t._obs.shape[0]) for t in trainers]
+    if any(r != rows[0] for r in rows):
+        raise ValueError(f"train_backward_many: one row count per call, the forwards had {rows}")
+    rows = rows[0]
+    ws = [t._weights() for t in trainers]
+    for i, (w, dz, o) in enumerate(zip(ws, dlogits, outs)):       # every check before any native call
+        _check_rows(dz, f"dlogits[{i}]", NUM_ACTIONS, dev)
+        if dz.shape[0] != rows:
+            raise ValueError(f"dlogits[{i}]: expected {rows} rows, got {dz.shape[0]}")
+        if o is None:
+            continue
+        if not isinstance(o, dict) or sorted(o) != sorted(KEYS):
+            raise ValueError(f"out[{i}]: None or a dict of the six keys {KEYS}")
+        for k in KEYS:
+            _check_out(o[k], w[k].shape, torch.float32, dev)
+            if any(p is not None and p[k].data_ptr() == o[k].data_ptr() for p in outs[:i]):
+                raise ValueError(f"out[{i}][{k!r}]: two trainers' gradients in one tensor")
+    jobs, res = [], []
+    for t, w, dz, o in zip(trainers, ws, dlogits, outs):
+        grads = {k: t._own("g" + k, w[k].shape) for k in KEYS} if o is None else dict(o)
+        h0, h1 = t._own("h0", (rows, dims[1])), t._own("h1", (rows, dims[2]))
+        work = t._own("work", (work_bytes(dims, rows),), torch.uint8)
+        jobs.append(nat.WhMlpTrainJob(_struct(w), _ptr(t._obs), _ptr(h0), _ptr(h1), None, _ptr(dz),
+                                      _struct(grads), work.data_ptr()))
+        res.append(grads)
+    _run_many("wh_mlp_backward_multi", dims, dev, jobs, rows)
+    return res
