@@ -607,6 +607,13 @@ typedef struct wh_sac_td_args {
   float* td;               /* [M] out; may be NULL */
 } wh_sac_td_args;
 int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void* stream);
+/* wh_sac_td with alpha read where the arithmetic runs: alpha = expf(log_alpha[0]), a->alpha is
+ * ignored; everything else is wh_sac_td's.  This is how wh_sac_loss forms its alpha, so the target and
+ * the losses of one update use the same value, and a learner needs no host read (nor a stream
+ * capture a frozen value).  log_alpha: [1] f32, device memory (host memory on the host engine).
+ * WH_EINVAL: wh_sac_td's, and for M > 0 log_alpha == NULL.  M = 0 launches nothing.  Both engines
+ * implement it; expf is each engine's own, as in SAC LOSSES (expf(0) = 1 on both). */
+int wh_sac_td_la(int64_t M, int32_t NA, const wh_sac_td_args* a, const float* log_alpha, void* stream);
 
 /* SAC LOSSES: the critic, actor and alpha losses of RLlib's discrete SAC (sac_tf_policy, discrete
  * branch) and d(loss)/d(logits), from the learner's own logits at `obs` (what wh_mlp_train_forward
@@ -680,6 +687,30 @@ typedef struct wh_adam_hyper {
 } wh_adam_hyper;
 #define WH_ADAM_MAX_SEGS 24
 int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, void* stream);
+/* wh_adam_step with the step count where the arithmetic runs.  One call advances `clock` and then
+ * steps the tensors from clock->h, in stream order, with no host read: a one-lane launch ticks the
+ * clock, the launch after it reads the table (no grid-wide barrier, no flag).  The tick, in double:
+ *   t += 1 ;  beta1_t *= beta1 ;  beta2_t *= beta2
+ *   h = {beta1, 1 - beta1, beta2, 1 - beta2, eps, lr / (1 - beta1_t), sqrt(1 - beta2_t)}
+ * each value rounded to f32 once, no fused multiply-adds.  beta^t is a running product, not pow, so
+ * that the engines agree bit for bit: IEEE double multiply, subtract, divide and sqrt are correctly
+ * rounded on both.  Confirmed for gfx950 from the compiled tick (the divide and the square root are
+ * the compiler's v_rcp_f64 / v_rsq_f64 Newton expansions with their v_div_scale / v_div_fmas /
+ * v_div_fixup and exponent-scaling fix-ups, which round correctly; no v_fma on the products or the
+ * subtractions) and by tests/test_gpu_sync_free.py, which holds the device's clock and tensors to the
+ * host engine's bit for bit over 20 chained steps.  Against lr / (1 - beta1 ** t) and
+ * sqrt(1 - beta2 ** t) computed with pow, h is equal at t = 1 and within one f32 ulp per field later
+ * (the product differs from pow by about t * 2^-53 relative).  The element arithmetic is wh_adam_step's.
+ * A fresh clock is {0, 1.0, 1.0, any h}.
+ * WH_EINVAL: wh_adam_step's segment rules; clock == NULL or not 8-byte aligned.  nseg = 0 (and a call
+ * whose segments are all empty) still ticks.  Both engines implement it. */
+typedef struct wh_adam_clock {      /* device memory (host memory on the host engine), 8-byte aligned */
+  int64_t t;                        /* steps taken; 0 to start */
+  double beta1_t, beta2_t;          /* beta1^t, beta2^t as running products; 1.0 to start */
+  wh_adam_hyper h;                  /* the table of step t, written by the tick */
+} wh_adam_clock;
+int wh_adam_step_clock(int32_t nseg, const wh_adam_seg* segs, wh_adam_clock* clock,
+                       double lr, double beta1, double beta2, double eps, void* stream);
 
 /* Library build identification (e.g. "warehouse_amd gfx950 <date>"). */
 const char* wh_version(void);

@@ -403,6 +403,13 @@ inline int sac_td_call(int64_t M, int32_t NA, const wh_sac_td_args* a) {
   return (a->mask_dones != 0 && !a->dones) ? WH_EINVAL : WH_OK;
 }
 
+// wh_sac_td_la: wh_sac_td's rules, then -- for M > 0 -- the pointer alpha is read through.
+inline int sac_td_la_call(int64_t M, int32_t NA, const wh_sac_td_args* a, const float* log_alpha) {
+  const int rc = sac_td_call(M, NA, a);
+  if (rc || M == 0) return rc;
+  return log_alpha ? WH_OK : WH_EINVAL;
+}
+
 // ----------------------------------------------------------------------------- SAC losses
 // wh_sac_loss / wh_sac_loss_query: the sizes first, then -- for M > 0 only -- the pointers.  A
 // workgroup (and the host engine's unit of `work`) owns floor(256 / NA) whole samples, like wh_sac_td;
@@ -432,8 +439,7 @@ inline int sac_loss_call(int64_t M, int32_t NA, const wh_sac_loss_args* a) {
 // ----------------------------------------------------------------------------- Adam
 // wh_adam_step: the count of segments, h, segs, then every segment: its count, and for count > 0 its
 // four pointers, each 4-byte aligned.
-inline int adam_call(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h) {
-  if (nseg < 0 || nseg > WH_ADAM_MAX_SEGS || !h) return WH_EINVAL;
+inline int adam_segs(int32_t nseg, const wh_adam_seg* segs) {
   if (nseg > 0 && !segs) return WH_EINVAL;
   for (int32_t s = 0; s < nseg; ++s) {
     const wh_adam_seg& g = segs[s];
@@ -443,6 +449,17 @@ inline int adam_call(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper*
     if (((uintptr_t)g.p | (uintptr_t)g.m | (uintptr_t)g.v | (uintptr_t)g.g) & 3u) return WH_EINVAL;
   }
   return WH_OK;
+}
+
+inline int adam_call(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h) {
+  if (nseg < 0 || nseg > WH_ADAM_MAX_SEGS || !h) return WH_EINVAL;
+  return adam_segs(nseg, segs);
+}
+
+// wh_adam_step_clock: the count of segments, the clock and its alignment, then the segments as above.
+inline int adam_clock_call(int32_t nseg, const wh_adam_seg* segs, const wh_adam_clock* clock) {
+  if (nseg < 0 || nseg > WH_ADAM_MAX_SEGS || !clock || ((uintptr_t)clock & 7u)) return WH_EINVAL;
+  return adam_segs(nseg, segs);
 }
 
 // ----------------------------------------------------------------------------- MLP training

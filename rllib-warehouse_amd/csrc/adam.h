@@ -10,6 +10,10 @@
 // partial piece element by element); any other segment moves 4 bytes per access -- a choice that is
 // uniform per workgroup.  28 bytes per element (p, m, v read and written, g read) and a dozen flops:
 // bandwidth-bound by construction.
+//
+// Two instances of one body: k_adam takes the table of the step by value; k_adam_clock
+// (wh_adam_step_clock) reads it from the wh_adam_clock that k_adam_tick, one lane launched just before
+// it on the same stream, has advanced.  Stream order is the only ordering between the two.
 
 constexpr int ADAM_PPL = 2;                       // pieces per lane
 constexpr int ADAM_CHUNK = BT * ADAM_PPL * 4;     // elements a workgroup owns
@@ -21,7 +25,8 @@ struct AdamParams {
   int32_t nseg;
 };
 
-__global__ __launch_bounds__(BT) void k_adam(AdamParams P) {
+template <bool CLOCK>
+__device__ __forceinline__ void adam_body(const AdamParams& P, const wh_adam_clock* clock) {
   const uint32_t b = blockIdx.x;
   const int tid = threadIdx.x;
   int s = 0;                                      // the last segment that starts at or before b: an
@@ -32,7 +37,7 @@ __global__ __launch_bounds__(BT) void k_adam(AdamParams P) {
   const float* __restrict__ g = P.seg[s].g;
   const int64_t count = P.seg[s].count;
   const int64_t base = (int64_t)(b - P.start[s]) * ADAM_CHUNK;
-  const wh_adam_hyper h = P.h;
+  const wh_adam_hyper h = CLOCK ? clock->h : P.h;
   const bool vec = ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15u) == 0);   // (uniform)
   if (vec) {
 #pragma unroll
@@ -63,4 +68,22 @@ __global__ __launch_bounds__(BT) void k_adam(AdamParams P) {
       if (e < count) wh_sac::adam_element(h, g[e], p[e], m[e], v[e]);
     }
   }
+}
+
+__global__ __launch_bounds__(BT) void k_adam(AdamParams P) { adam_body<false>(P, nullptr); }
+
+__global__ __launch_bounds__(BT) void k_adam_clock(AdamParams P, const wh_adam_clock* clock) { adam_body<true>(P, clock); }
+
+// The tick of wh_adam_step_clock: one lane, sac_formula.h's adam_tick (shared with the host engine),
+// plain stores.
+struct AdamTickParams {
+  wh_adam_clock* clock;
+  double lr, beta1, beta2, eps;
+};
+
+__global__ __launch_bounds__(64) void k_adam_tick(AdamTickParams P) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  wh_adam_clock c = *P.clock;
+  wh_sac::adam_tick(c, P.lr, P.beta1, P.beta2, P.eps);
+  *P.clock = c;
 }

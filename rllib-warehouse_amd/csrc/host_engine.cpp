@@ -968,6 +968,15 @@ int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void*) {
   return WH_OK;
 }
 
+// alpha = expf(log_alpha[0]), as wh_sac_loss below forms it; the rest is wh_sac_td
+int wh_sac_td_la(int64_t M, int32_t NA, const wh_sac_td_args* a, const float* log_alpha, void* stream) {
+  const int rc = wh_abi::sac_td_la_call(M, NA, a, log_alpha);
+  if (rc || M == 0) return rc;
+  wh_sac_td_args b = *a;
+  b.alpha = expf(log_alpha[0]);
+  return wh_sac_td(M, NA, &b, stream);
+}
+
 // ---- SAC losses (include/warehouse_amd.h, SAC LOSSES): sac_formula.h's row arithmetic, the sums in
 // ascending row order; `work` is checked like the device's and not used
 int wh_sac_loss_query(int64_t M, int32_t NA, int64_t* work_bytes) { return wh_abi::sac_loss_query_call(M, NA, work_bytes); }
@@ -1018,6 +1027,15 @@ int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, 
     for (int64_t e = 0; e < g.count; ++e) wh_sac::adam_element(*h, g.g[e], g.p[e], g.m[e], g.v[e]);
   }
   return WH_OK;
+}
+
+// the tick (sac_formula.h's adam_tick, the device's), then the step from the table it wrote
+int wh_adam_step_clock(int32_t nseg, const wh_adam_seg* segs, wh_adam_clock* clock, double lr, double beta1,
+                       double beta2, double eps, void* stream) {
+  const int rc = wh_abi::adam_clock_call(nseg, segs, clock);
+  if (rc) return rc;
+  wh_sac::adam_tick(*clock, lr, beta1, beta2, eps);
+  return wh_adam_step(nseg, segs, &clock->h, stream);
 }
 
 // ---- what the CPU has no use for: the policy network and its fragment operand (device formats),

@@ -147,4 +147,32 @@ WH_SAC_HD inline void adam_element(const H& h, float g, float& p, float& m, floa
   v = v1;
 }
 
+// ---- wh_adam_step_clock: the tick (C: wh_adam_clock).  All in double -- IEEE multiply, subtract,
+// divide and sqrt, correctly rounded on both engines -- and each field of h rounded to f32 once.
+// 1 - beta^t * beta is a natural fused multiply-add, which would round once where the header rounds
+// twice: contraction is off by the pragma under clang (the device) and by the attribute under g++ (the
+// host engine), so the engines' equality does not rest on the host's -march having no FMA.
+#if defined(__GNUC__) && !defined(__clang__)
+#define WH_SAC_NO_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define WH_SAC_NO_CONTRACT
+#endif
+template <class C>
+WH_SAC_HD WH_SAC_NO_CONTRACT inline void adam_tick(C& c, double lr, double beta1, double beta2, double eps) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const double b1t = c.beta1_t * beta1, b2t = c.beta2_t * beta2;
+  c.t = c.t + 1;
+  c.beta1_t = b1t;
+  c.beta2_t = b2t;
+  c.h.beta1 = (float)beta1;
+  c.h.omb1 = (float)(1.0 - beta1);
+  c.h.beta2 = (float)beta2;
+  c.h.omb2 = (float)(1.0 - beta2);
+  c.h.eps = (float)eps;
+  c.h.step_size = (float)(lr / (1.0 - b1t));
+  c.h.sqrt_bc2 = (float)sqrt(1.0 - b2t);
+}
+
 }  // namespace wh_sac

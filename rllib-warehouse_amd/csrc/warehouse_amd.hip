@@ -963,6 +963,17 @@ int wh_sac_td(int64_t M, int32_t NA, const wh_sac_td_args* a, void* stream) {
   return hip_err(hipGetLastError());
 }
 
+int wh_sac_td_la(int64_t M, int32_t NA, const wh_sac_td_args* a, const float* log_alpha, void* stream) {
+  const int rc = wh_abi::sac_td_la_call(M, NA, a, log_alpha);
+  if (rc || M == 0) return rc;
+  const int32_t spw = BT / NA;
+  const int64_t groups = (M + spw - 1) / spw;
+  if (groups > 0x7FFFFFFF) return WH_EINVAL;
+  const SacParams p{*a, M, NA, spw};
+  hipLaunchKernelGGL(k_sac_la_td, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p, log_alpha);
+  return hip_err(hipGetLastError());
+}
+
 // ---- SAC losses (csrc/sac_loss.h): one launch, and for more than one workgroup the launch that adds
 // their partial sums
 int wh_sac_loss_query(int64_t M, int32_t NA, int64_t* work_bytes) { return wh_abi::sac_loss_query_call(M, NA, work_bytes); }
@@ -982,22 +993,44 @@ int wh_sac_loss(int64_t M, int32_t NA, const wh_sac_loss_args* a, void* stream) 
 }
 
 // ---- Adam (csrc/adam.h): the segment table and every segment's first workgroup go in the argument
-int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, void* stream) {
-  const int rc = wh_abi::adam_call(nseg, segs, h);
-  if (rc || nseg == 0) return rc;
-  AdamParams p{};
+static int adam_params(int32_t nseg, const wh_adam_seg* segs, AdamParams* p, int64_t* groups_out) {
   int64_t groups = 0;
   for (int32_t s = 0; s < nseg; ++s) {
-    p.seg[s] = segs[s];
-    p.start[s] = (uint32_t)groups;
+    p->seg[s] = segs[s];
+    p->start[s] = (uint32_t)groups;
     groups += (segs[s].count + ADAM_CHUNK - 1) / ADAM_CHUNK;
     if (groups > 0x7FFFFFFF) return WH_EINVAL;
   }
-  p.start[nseg] = (uint32_t)groups;
+  p->start[nseg] = (uint32_t)groups;
+  p->nseg = nseg;
+  *groups_out = groups;
+  return WH_OK;
+}
+
+int wh_adam_step(int32_t nseg, const wh_adam_seg* segs, const wh_adam_hyper* h, void* stream) {
+  int rc = wh_abi::adam_call(nseg, segs, h);
+  if (rc || nseg == 0) return rc;
+  AdamParams p{};
+  int64_t groups = 0;
+  if ((rc = adam_params(nseg, segs, &p, &groups))) return rc;
   p.h = *h;
-  p.nseg = nseg;
   if (groups == 0) return WH_OK;
   hipLaunchKernelGGL(k_adam, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p);
+  return hip_err(hipGetLastError());
+}
+
+// the tick, then -- in stream order -- the step that reads the table the tick wrote
+int wh_adam_step_clock(int32_t nseg, const wh_adam_seg* segs, wh_adam_clock* clock, double lr, double beta1,
+                       double beta2, double eps, void* stream) {
+  int rc = wh_abi::adam_clock_call(nseg, segs, clock);
+  if (rc) return rc;
+  AdamParams p{};
+  int64_t groups = 0;
+  if ((rc = adam_params(nseg, segs, &p, &groups))) return rc;   // (before the tick: a refused call changes nothing)
+  const AdamTickParams tick{clock, lr, beta1, beta2, eps};
+  hipLaunchKernelGGL(k_adam_tick, dim3(1), dim3(64), 0, (hipStream_t)stream, tick);
+  if (groups > 0)
+    hipLaunchKernelGGL(k_adam_clock, dim3((unsigned)groups), dim3(BT), 0, (hipStream_t)stream, p, clock);
   return hip_err(hipGetLastError());
 }
 

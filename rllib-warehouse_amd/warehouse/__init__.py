@@ -16,13 +16,13 @@ from .replay import ReplayBuffer  # noqa: F401
 from .sac import QNetwork, SACCritic  # noqa: F401
 from .policy import forward_many, policy_collect  # noqa: F401
 from .train import MLPTrainer, mlp_logits, train_backward_many, train_forward_many  # noqa: F401
-from .learner import DeviceAdam, SACLearner, sac_losses  # noqa: F401
+from .learner import CapturedUpdate, DeviceAdam, SACLearner, sac_losses  # noqa: F401
 
 __all__ = []
 __all__.extend(core.__all__)
 __all__.extend(variants.__all__)
 __all__ += ["BatchedWarehouse", "EpisodeStats", "WarehouseVectorEnv", "WarehouseBaseEnv", "ReplayBuffer",
             "SACCritic", "QNetwork", "forward_many", "policy_collect", "MLPTrainer", "mlp_logits",
-            "SACLearner", "DeviceAdam", "sac_losses"]
+            "SACLearner", "DeviceAdam", "sac_losses", "CapturedUpdate"]
 
 name = "warehouse"

@@ -51,7 +51,8 @@ SYMBOLS = ("wh_query", "wh_pack", "wh_unpack", "wh_reset", "wh_step", "wh_observ
            "wh_mlp_pack_device", "wh_sac_td", "wh_mlp_forward_multi",
            "wh_mlp_train_query", "wh_mlp_train_forward", "wh_mlp_backward",
            "wh_mlp_train_forward_multi", "wh_mlp_backward_multi",
-           "wh_sac_loss_query", "wh_sac_loss", "wh_adam_step")
+           "wh_sac_loss_query", "wh_sac_loss", "wh_adam_step",
+           "wh_sac_td_la", "wh_adam_step_clock")
 
 WH_PRIO_ONE = 1 << 20          # fixed-point priority 1.0 of the replay priority tree
 WH_PRIO_MAX = 0x7FFFFFFF       # the largest stored priority
@@ -181,6 +182,20 @@ def adam_hyper(lr: float, beta1: float, beta2: float, eps: float, t: int) -> WhA
     return WhAdamHyper(beta1, 1.0 - beta1, beta2, 1.0 - beta2, eps, lr / (1.0 - beta1 ** t), (1.0 - beta2 ** t) ** 0.5)
 
 
+class WhAdamClock(ctypes.Structure):   # wh_adam_clock: 56 bytes, 8-byte aligned, where wh_adam_step_clock runs
+    _fields_ = [("t", ctypes.c_int64), ("beta1_t", ctypes.c_double), ("beta2_t", ctypes.c_double), ("h", WhAdamHyper)]
+
+
+def adam_clock(t: int, beta1: float, beta2: float) -> WhAdamClock:
+    """The wh_adam_clock after t steps: beta^t as the running product the tick forms (t multiplications
+    in double, not pow), and a zero table (the next tick writes it)."""
+    b1t = b2t = 1.0
+    for _ in range(int(t)):
+        b1t *= beta1
+        b2t *= beta2
+    return WhAdamClock(int(t), b1t, b2t, WhAdamHyper())
+
+
 class WarehouseNativeError(RuntimeError):
     pass
 
@@ -282,6 +297,9 @@ def _load(path: str, ab: bool) -> ctypes.CDLL:
     S.wh_sac_loss_query.argtypes = [_I64, _I32, ctypes.POINTER(ctypes.c_int64)]
     S.wh_sac_loss.argtypes = [_I64, _I32, ctypes.POINTER(WhSacLossArgs), _P]
     S.wh_adam_step.argtypes = [_I32, ctypes.POINTER(WhAdamSeg), ctypes.POINTER(WhAdamHyper), _P]
+    S.wh_sac_td_la.argtypes = [_I64, _I32, ctypes.POINTER(WhSacTdArgs), _P, _P]
+    _F64 = ctypes.c_double
+    S.wh_adam_step_clock.argtypes = [_I32, ctypes.POINTER(WhAdamSeg), _P, _F64, _F64, _F64, _F64, _P]
     S.wh_check_read.argtypes = [ctypes.POINTER(ctypes.c_uint64), _I32]
     S.wh_rollout_prepare.argtypes = [_CFG, _I64, _P, _I32, _I32, _F32, _P, _P, _P, _ST, _I32, _I32, _U64, _I64, _P,
                                      ctypes.POINTER(ctypes.c_void_p)]

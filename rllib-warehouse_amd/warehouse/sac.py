@@ -133,7 +133,10 @@ class SACCritic:
         forward_many(jobs)
         return outs
 
-    def _run(self, batch, out, with_q: bool) -> Dict[str, torch.Tensor]:
+    def _run(self, batch, out, with_q: bool, log_alpha=None) -> Dict[str, torch.Tensor]:
+        if log_alpha is not None and (not torch.is_tensor(log_alpha) or log_alpha.numel() != 1 or
+                                      log_alpha.dtype != torch.float32 or log_alpha.device != self.device):
+            raise ValueError(f"SACCritic: log_alpha is a one-element float32 tensor on {self.device}")
         for k in ("actions", "rewards"):
             if k not in batch:
                 raise ValueError(f"SACCritic: the batch lacks {k!r}")
@@ -156,38 +159,48 @@ class SACCritic:
         self.last_fused = self.use_fused(rows)
         if self.last_fused:
             pi, q1t, q2t, q1, q2 = self._forward_fused(batch, rows, with_q)
-            return self._epilogue(batch, res, M, NA, pi, q1t, q2t, q1, q2)
+            return self._epilogue(batch, res, M, NA, pi, q1t, q2t, q1, q2, log_alpha)
         pi = self._forward(self.policy, batch, "next_", rows, "pi_next")
         q1t = self._forward(self.q1_target, batch, "next_", rows, "q1t_next")
         q2t = self._forward(self.q2_target, batch, "next_", rows, "q2t_next") if self.q2_target is not None else None
         q1 = self._forward(self.q1, batch, "", rows, "q1") if with_q else None
         q2 = self._forward(self.q2, batch, "", rows, "q2") if with_q and self.q2 is not None else None
-        return self._epilogue(batch, res, M, NA, pi, q1t, q2t, q1, q2)
+        return self._epilogue(batch, res, M, NA, pi, q1t, q2t, q1, q2, log_alpha)
 
-    def _epilogue(self, batch, res, M, NA, pi, q1t, q2t, q1, q2):
+    def _epilogue(self, batch, res, M, NA, pi, q1t, q2t, q1, q2, log_alpha=None):
         n, dones = batch.get("n"), batch.get("dones")
         args = nat.WhSacTdArgs(pi.data_ptr(), q1t.data_ptr(), nat.ptr(q2t), nat.ptr(q1), nat.ptr(q2),
                                nat.ptr(batch["actions"]), nat.ptr(batch["rewards"]), nat.ptr(dones), nat.ptr(n),
                                self.alpha, self.gamma ** self.n_step, int(self.mask_dones),
                                nat.ptr(res.get("y")), nat.ptr(res.get("td_rows")), nat.ptr(res.get("td")))
+        if log_alpha is not None:   # alpha = exp(log_alpha[0]) on the device; args.alpha is ignored
+            nat.check(nat.lib().wh_sac_td_la(M, NA, ctypes.byref(args), log_alpha.data_ptr(),
+                                             nat.stream_of(self.device)), "wh_sac_td_la")
+            return res
         nat.check(nat.lib().wh_sac_td(M, NA, ctypes.byref(args), nat.stream_of(self.device)), "wh_sac_td")
         return res
 
     # ------------------------------------------------------------------ the surface
-    def td(self, batch: Dict[str, torch.Tensor], *, out: Optional[Dict[str, torch.Tensor]] = None):
+    def td(self, batch: Dict[str, torch.Tensor], *, out: Optional[Dict[str, torch.Tensor]] = None,
+           log_alpha: Optional[torch.Tensor] = None):
         """`batch`: a ReplayBuffer.sample(..., fragments=True) dict (bf16 networks read the xfrag /
         next_xfrag operands), or one with rows (obs / next_obs; what f32-precision networks read).
         Runs the policy and the target Q networks on the next side and the Q networks on the obs
         side (five forwards, three without a twin), then wh_sac_td.  Returns {"y" [M,NA], "td_rows"
         [M,NA], "td" [M]}: the critic's own tensors, overwritten by its next call, or the caller's
         through `out` (any of the three keys).  td[m] is one TD error per ring entry, the mean over
-        its live agent rows: `buf.update_priorities(batch["idx_out"], out["td"])`."""
-        return self._run(batch, out, True)
+        its live agent rows: `buf.update_priorities(batch["idx_out"], out["td"])`.  `log_alpha`: None
+        uses `self.alpha`; a one-element float32 tensor on the critic's device makes the kernel read it
+        and use alpha = exp(log_alpha) (wh_sac_td_la): no host read, and the value a replayed stream
+        capture sees is the one in memory then."""
+        return self._run(batch, out, True, log_alpha)
 
-    def targets(self, batch: Dict[str, torch.Tensor], *, out: Optional[Dict[str, torch.Tensor]] = None):
+    def targets(self, batch: Dict[str, torch.Tensor], *, out: Optional[Dict[str, torch.Tensor]] = None,
+                log_alpha: Optional[torch.Tensor] = None):
         """Only the three next-side forwards and {"y"}: for a learner that wants the target without
-        gradient and computes Q(obs) itself under autograd.  The same `y` as td(), bit for bit."""
-        return self._run(batch, out, False)
+        gradient and computes Q(obs) itself under autograd.  The same `y` as td(), bit for bit
+        (`log_alpha` as in td())."""
+        return self._run(batch, out, False, log_alpha)
 
     def sync_targets(self) -> None:
         """q1_target <- q1 and q2_target <- q2 (MLPPolicy.copy_from): the YAMLs' hard target update."""
